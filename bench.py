@@ -1,6 +1,6 @@
 """Self-play throughput benchmark: games/sec at 400 MCTS simulations per move.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU, RCCL)
 
 Workload (BASELINE.json configs[2], the one the metric is quoted on): 8x8 Othello,
@@ -29,7 +29,13 @@ move completions).  The window also contains the per-generation RCCL all-gather 
 finished games' samples.  The move-completion rate and the games that actually finished in
 the window are reported beside it.
 
-Also measured in the same run:
+--dump-outputs DIR writes what the timed window's last step left for a caller, one float32 /
+float64 DIR/<name>.npy each (dump_arrays; at most 64 MB in all, a seeded row sample above that):
+the last step's leaf planes with the net's priors and values for them, every slot's root visit
+counts and value, the window's sample rows (ordered by slot) and the counters.  The seeds are
+fixed, so the same arguments give the same inputs in every run.
+
+A plain run measures only the headline figure.  With --full also measured in the same run:
   roofline      the bitboard-step kernel (oth_step_gpu, the north-star kernel) on 2^24
                 positions of seeded random playouts, timed before the
                 self-play warmup and again after the window: 43 algorithmic bytes per
@@ -141,10 +147,19 @@ def parse():
     ap.add_argument("--cpu-workers", type=int, default=None,
                     help="host cores (one single-threaded process each) for cpu_baseline; "
                          "default: every CPU allotted to this job (host_cpu_share)")
-    ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the kernel rooflines (roofline, roofline_conv, "
+                         "roofline_trunk) and the CPU baseline (cpu_baseline); a plain run "
+                         "measures the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what their last step computed as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--skip-cpu", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--skip-kernel", action="store_true", help="--full without the rooflines")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "oth_step_traffic.json"))
     a = ap.parse_args()
+    if not a.full:  # the rooflines and the CPU baseline are --full's
+        a.skip_cpu = a.skip_kernel = True
     preset = {"c2": (4096, 100, "fast", False, "fp32"), "c3": (1024, 400, "az5x128", False, "fp32"),
               "arena": (1024, 400, "az5x128", False, "fp32"),
               "c4": (4096, 400, "az5x128", False, "fp32"),
@@ -732,6 +747,64 @@ def aggregate_stats(allst, sims_per_move):
                          for r in allst]}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_arrays(dirpath, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: every array of `arrays` as dirpath/<name>.npy, float64 kept and every
+    other type as float32.  Above max_bytes in all, the arrays of 1 MiB and more keep a
+    sample of their rows in proportion (drawn once from seed 0 per row count, in row order: the
+    same rows in every run, and the same rows of arrays with equal row counts)."""
+    os.makedirs(dirpath, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64
+                                   else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > max_bytes:
+        big = {k for k, v in out.items() if v.nbytes >= 1 << 20 and v.ndim >= 1}
+        small = total - sum(out[k].nbytes for k in big)
+        frac = max(0.0, (max_bytes - small)) / max(1, total - small)
+        for k in sorted(big):
+            rows = out[k].shape[0]
+            keep = np.sort(np.random.default_rng(0).permutation(rows)[:int(rows * frac)])
+            out[k] = np.ascontiguousarray(out[k][keep])
+    assert sum(v.nbytes for v in out.values()) <= max_bytes
+    for k, v in out.items():
+        np.save(os.path.join(dirpath, k + ".npy"), v)
+    return out
+
+
+def selfplay_outputs(sp, c0, c1):
+    """What a caller of the timed path holds after its last step (sp: BatchedSelfPlay or
+    PipelinedSelfPlay, c0 / c1: counters() before and after the window): the last step's
+    evaluation rows (row g*K + j = leaf j of slot g: the packed planes, the net's priors and
+    values), every slot's root visit counts and value, the sample rows recorded in the window
+    (games reserve their rows in the order they happen to finish, so sorted by slot: a slot's
+    rows stay in game and ply order) and the counters."""
+    import az_native as nat
+
+    parts = getattr(sp, "parts", [sp])
+    torch.cuda.synchronize()
+    cat = lambda xs: torch.cat([x.detach().float().cpu() for x in xs]).numpy()  # noqa: E731
+    out = {"leaf_planes": cat([p.engine.nn_in for p in parts]),
+           "priors": cat([p.engine.priors for p in parts]),
+           "values": cat([p.engine.values for p in parts])}
+    stats = [p.engine.root_stats() for p in parts]
+    out["root_visits"] = np.concatenate([s[0] for s in stats])
+    out["root_value"] = np.concatenate([s[1] for s in stats])
+    rows = sp.samples_since(c0)
+    order = np.argsort(rows["slot"], kind="stable")
+    rows = {k: v[order] for k, v in rows.items()}
+    n = len(order)
+    out["sample_state"] = (nat.unpack_np(rows["own"], rows["opp"], np.ones(n, np.int8))
+                           .reshape(n, 64) if n else np.zeros((0, 64), np.int8))
+    out["sample_pi"], out["sample_z"] = rows["pi"], rows["z"]
+    out["sample_player"], out["sample_slot"] = rows["player"], rows["slot"]
+    keys = ("games_started", "games_finished", "samples", "samples_dropped", "arena_overflows",
+            "steps", "simulations", "moves")
+    out["counters"] = np.array([c1[k] for k in keys], np.float64)
+    return out
+
+
 def main_arena(a):
     """eval.py's evaluate_models_parallel (eval.py:47-74) with play_match (:134-178) per match,
     as arena.BatchedArena plays it: matches/s.  Two random-init nets of configs[2]'s
@@ -762,6 +835,9 @@ def main_arena(a):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     its = arena.iterations - it0
+    if a.dump_outputs:  # what arena.play returned: the tallies and every match's length
+        dump_arrays(a.dump_outputs, {"wins_draws": np.array([wa, wb, dr], np.float64),
+                                     "plies": np.asarray(plies)})
     result = {
         "metric": f"arena matches/sec (eval.py play_match), 8x8 Othello @ {a.sims} MCTS sims/move",
         "value": round(n / dt, 4), "unit": "matches/s", "n_gpus": 1, "steps": its,
@@ -890,6 +966,8 @@ def main():
     dt = time.perf_counter() - t0
     prof.pause()
     c1 = sp.counters()
+    if a.dump_outputs and rank == 0:
+        dump_arrays(a.dump_outputs, selfplay_outputs(sp, c0, c1))
     # AZ_BENCH_REPEAT=k (diagnostics): k more windows of the same length after the timed one,
     # timed the same way, reported beside the line (never part of value)
     repeat = []
