@@ -30,6 +30,8 @@ AZ_FLAG_NOPLACE = 2
 AZ_FLAG_ILLEGAL = 4
 AZ_FLAG_PASSED = 8
 
+AZ_SOLVE_SKIPPED, AZ_SOLVE_ABORTED, AZ_SOLVE_MAX_EMPTIES = -128, -127, 14
+
 AZ_EVAL_EXTERNAL, AZ_EVAL_ROLLOUT = 0, 1
 AZ_RNG_DEVICE, AZ_RNG_INJECTED = 0, 1
 AZ_GAME_IDLE, AZ_GAME_ACTIVE, AZ_GAME_FINISHED, AZ_GAME_SEARCH_DONE = 0, 1, 2, 3
@@ -140,6 +142,8 @@ SIGNATURES = {
     "az_conv3x3_mx_cfg_gpu": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],
     "az_conv3x3_mx_stem_gpu": [_P] * 7 + [_I32, _I32, _I32, _I32, _P],
     "az_replay_aggregate_gpu": [_P] * 5 + [_I64] + [_P] * 10,
+    "oth_solve_cpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
+    "oth_solve_gpu": [_P, _P, _I64, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
 }
 
 
@@ -271,6 +275,18 @@ def d4_cpu(x, sym):
     out = np.empty(x.shape, np.uint64)
     check(lib.oth_d4_cpu(ptr(x), ptr(sym), ptr(out), x.size), "oth_d4_cpu")
     return out
+
+
+def solve_cpu(own, opp, max_empties=12, node_limit=1 << 31):
+    """Exact endgame solve on the host: (score int8, best uint8, nodes uint64) per position
+    (AZ_SOLVE_SKIPPED / AZ_SOLVE_ABORTED in score for positions not solved)."""
+    own, opp = _u64(own), _u64(opp)
+    score = np.empty(own.shape, np.int8)
+    best = np.empty(own.shape, np.uint8)
+    nodes = np.empty(own.shape, np.uint64)
+    check(lib.oth_solve_cpu(ptr(own), ptr(opp), own.size, int(max_empties), int(node_limit),
+                            ptr(score), ptr(best), ptr(nodes)), "oth_solve_cpu")
+    return score, best, nodes
 
 
 def status_flags(st):

@@ -1,0 +1,203 @@
+"""Exact endgame solver: game-theoretic scores, best moves and exact value targets.
+
+`solve` runs the native alpha-beta (csrc/solve.h) over a batch of positions, on the GPU
+(oth_solve_gpu: one lane per search, refilled from a queue) when there is one, else on the
+host (oth_solve_cpu over a thread pool; ctypes releases the GIL).  On top of it:
+
+* `relabel_rows` replaces the self-play value target z of late positions by the exact
+  win / draw / loss, and
+* `move_report` measures the search's preferred move (argmax pi) against the exact result:
+  how often it is optimal, how often it keeps the win / draw / loss, how many discs it gives
+  away.
+
+score = final own - opp disc difference from the side to move's view (the reference's plain
+count, envs/othello.py:214-220), best = the lowest optimal action (64 = pass).
+"""
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+import az_native as nat
+
+# fastest on the 1..12-empties corpus workload (scripts/bench_solve.py,
+# profiles/solve_bench.json: 11.5 s against 15.2 s unsplit and 14.9 s at two plies; two plies
+# win when every root is hard: 3.2 s against 6.4 s on the 12-empties subset alone)
+DEFAULT_SPLIT_PLIES = 1
+MAX_THREADS = 16
+
+
+def _popcount(x):
+    x = np.ascontiguousarray(x, np.uint64)
+    return np.unpackbits(x.view(np.uint8).reshape(-1, 8), axis=1).sum(axis=1).astype(np.int64)
+
+
+def empties(own, opp):
+    """Empty squares per position (numpy uint64 bitboards)."""
+    return 64 - _popcount(np.asarray(own).view(np.uint64) | np.asarray(opp).view(np.uint64))
+
+
+def _solve_cpu(own, opp, max_empties, node_limit):
+    n = own.size
+    score, best = np.empty(n, np.int8), np.empty(n, np.uint8)
+    nodes = np.empty(n, np.uint64)
+    if n == 0 or max_empties > nat.AZ_SOLVE_MAX_EMPTIES or max_empties < 0:
+        # the library validates the arguments (and accepts n = 0)
+        nat.check(nat.lib.oth_solve_cpu(nat.ptr(own), nat.ptr(opp), n, int(max_empties),
+                                        int(node_limit), nat.ptr(score), nat.ptr(best),
+                                        nat.ptr(nodes)), "oth_solve_cpu")
+        return score, best, nodes
+    threads = min(MAX_THREADS, n)
+    # interleaved chunks much smaller than a thread's share: the cost per position is
+    # heavy-tailed, so the hard ones must not all land in one thread's slice
+    size = max(1, min(256, n // (threads * 8) or 1))
+    bounds = [(a, min(n, a + size)) for a in range(0, n, size)]
+
+    def run(ab):
+        a, b = ab
+        return nat.lib.oth_solve_cpu(nat.ptr(own[a:b]), nat.ptr(opp[a:b]), b - a,
+                                     int(max_empties), int(node_limit), nat.ptr(score[a:b]),
+                                     nat.ptr(best[a:b]), nat.ptr(nodes[a:b]))
+
+    if threads == 1:
+        rcs = [run(ab) for ab in bounds]
+    else:
+        with ThreadPoolExecutor(threads) as ex:
+            rcs = list(ex.map(run, bounds))
+    for rc in rcs:
+        nat.check(rc, "oth_solve_cpu")
+    return score, best, nodes
+
+
+def solve_gpu_tensors(own, opp, max_empties, node_limit, split_plies, stream=None):
+    """oth_solve_gpu on int64 device tensors (the uint64 bitboards' bits), asynchronous on
+    `stream` (default: the current stream).  Returns device tensors (score int8, best uint8,
+    nodes int64 = the uint64 counts' bits)."""
+    dev = own.device
+    n = own.numel()
+    score = torch.empty(n, dtype=torch.int8, device=dev)
+    best = torch.empty(n, dtype=torch.uint8, device=dev)
+    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    import ctypes
+
+    need = ctypes.c_size_t(0)
+    args = (int(max_empties), int(node_limit), int(split_plies))
+    nat.check(nat.lib.oth_solve_gpu(None, None, n, *args, None, None, None, None,
+                                    ctypes.byref(need), None), "oth_solve_gpu")
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            ws = torch.empty(max(need.value, 8), dtype=torch.uint8, device=dev)
+            nat.check(nat.lib.oth_solve_gpu(nat.ptr(own), nat.ptr(opp), n, *args, nat.ptr(score),
+                                            nat.ptr(best), nat.ptr(nodes), nat.ptr(ws),
+                                            ctypes.byref(need), nat.stream_ptr(s)),
+                      "oth_solve_gpu")
+    return score, best, nodes
+
+
+def _pick_device(device, *arrays):
+    if device is not None:
+        return torch.device(device)
+    for a in arrays:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.device
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
+        else torch.device("cpu")
+
+
+def _as_i64_tensor(a, dev):
+    if isinstance(a, torch.Tensor):
+        assert a.dtype == torch.int64, "bitboard tensors are int64 (the uint64's bits)"
+        return a.reshape(-1).contiguous().to(dev)
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).reshape(-1).view(np.int64)).to(dev)
+
+
+def _as_u64_numpy(a):
+    if isinstance(a, torch.Tensor):
+        return a.detach().cpu().contiguous().numpy().reshape(-1).view(np.uint64)
+    return np.ascontiguousarray(a, np.uint64).reshape(-1)
+
+
+def solve(own, opp, max_empties=12, device=None, node_limit=1 << 31, split_plies=None):
+    """Exact solve of every position (own = side to move) with at most `max_empties`
+    empties: returns (score int8, best uint8, nodes uint64).  Positions with more empties
+    (or overlapping boards) get score AZ_SOLVE_SKIPPED (-128) and best 255; a search beyond
+    `node_limit` nodes gets AZ_SOLVE_ABORTED (-127).
+
+    own / opp: numpy uint64 arrays (numpy results) or torch int64 tensors holding the same
+    bits (torch results on the tensors' device, nodes as int64 bits).  device None = the GPU
+    when one is available, else the host; "cpu" forces the host path (thread pool of at most
+    16 threads).  split_plies (GPU only) None = DEFAULT_SPLIT_PLIES."""
+    want_torch = isinstance(own, torch.Tensor)
+    dev = _pick_device(device, own, opp)
+    if dev.type == "cuda":
+        sp = DEFAULT_SPLIT_PLIES if split_plies is None else int(split_plies)
+        s, b, nd = solve_gpu_tensors(_as_i64_tensor(own, dev), _as_i64_tensor(opp, dev),
+                                     max_empties, node_limit, sp)
+        if want_torch:
+            return s, b, nd
+        return s.cpu().numpy(), b.cpu().numpy(), nd.cpu().numpy().view(np.uint64)
+    s, b, nd = _solve_cpu(_as_u64_numpy(own), _as_u64_numpy(opp), max_empties, node_limit)
+    if want_torch:
+        return (torch.from_numpy(s).to(own.device), torch.from_numpy(b).to(own.device),
+                torch.from_numpy(nd.view(np.int64)).to(own.device))
+    return s, b, nd
+
+
+def _check_solved(score, what):
+    if (score == nat.AZ_SOLVE_ABORTED).any():
+        raise RuntimeError(f"{what}: {int((score == nat.AZ_SOLVE_ABORTED).sum())} searches "
+                           "exceeded the node limit")
+
+
+def relabel_rows(rows, max_empties, device=None):
+    """Exact value targets: in engine sample rows (dict of own / opp / pi / z / player, z
+    already from the side to move's view: canonical rows) replace z by float(sign(score)) for
+    every row whose position has 1..max_empties empties; other rows and fields are untouched.
+    Returns (rows, mask) with mask the boolean array of relabelled rows; `rows` is a new
+    dict sharing every array but z."""
+    own, opp = _as_u64_numpy(rows["own"]), _as_u64_numpy(rows["opp"])
+    e = empties(own, opp)
+    mask = (e >= 1) & (e <= int(max_empties)) & ((own & opp) == 0)
+    out = dict(rows)
+    z = np.array(np.asarray(rows["z"]), dtype=np.float64, copy=True)
+    if mask.any():
+        score, _, _ = solve(own[mask], opp[mask], max_empties, device=device)
+        _check_solved(score, "relabel_rows")
+        z[mask] = np.sign(score.astype(np.int64)).astype(np.float64)
+    out["z"] = z
+    return out, mask
+
+
+def _stats(score, value):
+    n = len(score)
+    if n == 0:
+        return {"n": 0, "optimal_frac": None, "wld_kept_frac": None, "mean_disc_loss": None}
+    return {"n": int(n), "optimal_frac": float((value == score).mean()),
+            "wld_kept_frac": float((np.sign(value) == np.sign(score)).mean()),
+            "mean_disc_loss": float((score - value).mean())}
+
+
+def move_report(rows, max_empties, device=None):
+    """How good is the search's preferred move a = argmax(pi) in every row with
+    1..max_empties empties?  The value of a is minus the exact score of the position after it
+    (made with the batched board step; after a placement or a pass the other side is to
+    move), compared with the position's own exact score; roots and children are solved in
+    one batch.  Returns {"by_empties": {e: stats}, "total": stats} with stats = n,
+    optimal_frac (value of a == score), wld_kept_frac (same sign) and mean_disc_loss
+    (score - value of a, in discs)."""
+    own, opp = _as_u64_numpy(rows["own"]), _as_u64_numpy(rows["opp"])
+    e = empties(own, opp)
+    mask = (e >= 1) & (e <= int(max_empties)) & ((own & opp) == 0)
+    own, opp, e = own[mask], opp[mask], e[mask]
+    pi = np.asarray(rows["pi"], np.float32).reshape(-1, 65)[mask]
+    act = pi.argmax(axis=1).astype(np.uint8)
+    cown, copp, _, _ = nat.step_cpu(own, opp, act)
+    n = len(own)
+    score, _, _ = solve(np.concatenate([own, cown]), np.concatenate([opp, copp]), max_empties,
+                        device=device)
+    _check_solved(score, "move_report")
+    score = score.astype(np.int64)
+    root, value = score[:n], -score[n:]
+    by = {int(k): _stats(root[e == k], value[e == k]) for k in range(1, int(max_empties) + 1)}
+    return {"by_empties": by, "total": _stats(root, value)}

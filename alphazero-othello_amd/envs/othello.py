@@ -164,6 +164,19 @@ class OthelloGameNew(Game):
     def get_opponent(self, player):
         return -player
 
+    def solve(self, state, player, max_empties=12):
+        """Exact endgame result of `state` with `player` to move (not in the reference): the
+        final disc difference for `player` under best play by both sides and the lowest
+        optimal action (64 = pass), from the native solver on the host.  Raises ValueError
+        when the position has more than `max_empties` empties."""
+        own, opp = self._bb(state, player)
+        score, best, _ = nat.solve_cpu(own, opp, max_empties)
+        if score[0] == nat.AZ_SOLVE_SKIPPED:
+            raise ValueError(f"position has more than {max_empties} empties")
+        if score[0] == nat.AZ_SOLVE_ABORTED:
+            raise RuntimeError("endgame search exceeded its node limit")
+        return int(score[0]), int(best[0])
+
     def print_board(self, state, player, ply=None):
         """The reference's text rendering (envs/othello.py:459-498)."""
         lines = ["  a b c d e f g h"]

@@ -346,7 +346,7 @@ def _one_game(args_tuple):
 
 def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, stream_id=0,
                             d4_augment=False, dtype=torch.float32, group=None,
-                            sync_weights=True, pipelines=1):
+                            sync_weights=True, pipelines=1, exact_endgame=0):
     """Batched replacement of Trainer.collect_self_play_games' pool (train.py:199-225):
     `num_games` games on the GPU, `n_slots` at a time (default min(games, 4096)), each
     searching with args['num_threads'] virtual-loss leaves per step (the reference's worker
@@ -363,7 +363,13 @@ def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, strea
 
     pipelines > 1: the rank's slots as that many independent pipelines on their own HIP
     streams (engine.PipelinedSelfPlay; +8-10 % on configs[1] / configs[4]-sized batches,
-    profiles/r04_pipelines_ab.json)."""
+    profiles/r04_pipelines_ab.json).
+
+    exact_endgame = E > 0: every row whose position has 1..E empties gets the exact
+    game-theoretic target z = sign(score) from the endgame solver (endgame.relabel_rows, on
+    each rank's own rows before the all-gather) instead of the played game's outcome.  Only
+    those rows change: with lambda < 1 the earlier rows keep their TD(lambda) targets, which
+    were built from the played outcome.  0 (the default) leaves the rows as they are."""
     import torch.distributed as dist
 
     distributed = dist.is_available() and dist.is_initialized() and \
@@ -371,7 +377,7 @@ def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, strea
     if not distributed:
         rows = _local_rows(policy, args, num_games, n_slots, seed, stream_id, d4_augment, dtype,
                            pipelines)
-        return _rows_to_tuples(rows)
+        return _rows_to_tuples(_exact_rows(rows, exact_endgame))
     from dist_replay import allgather_samples, broadcast_state_dict
 
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -383,8 +389,19 @@ def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, strea
     mine = num_games // world + (1 if rank < num_games % world else 0)
     rows = _local_rows(policy, args, mine, n_slots, seed, stream_id + rank, d4_augment, dtype,
                        pipelines)
+    rows = _exact_rows(rows, exact_endgame)
     pooled, _ = allgather_samples(rows, dev, group=group)
     return _rows_to_tuples({k: v.cpu().numpy() for k, v in pooled.items()})
+
+
+def _exact_rows(rows, exact_endgame):
+    """The rows with exact endgame targets for positions of 1..exact_endgame empties (0: the
+    rows themselves)."""
+    if exact_endgame <= 0 or len(rows["z"]) == 0:
+        return rows
+    from endgame import relabel_rows
+
+    return relabel_rows(rows, exact_endgame)[0]
 
 
 def _collective_device(group=None):

@@ -114,6 +114,39 @@ int oth_step_io_gpu(const uint64_t* own, const uint64_t* opp, const uint8_t* act
                     uint64_t* own_o, uint64_t* opp_o, uint64_t* legal_o, uint16_t* status_o,
                     int64_t n, void* stream);
 
+/* ---------------- exact endgame solver ---------------------------------------------
+ * For each position (own = side to move): score = the final popcount(own) - popcount(opp)
+ * from the root's side to move when both sides maximise it -- the reference's plain disc
+ * difference, empties to nobody (envs/othello.py:214-220); a side without a placement passes
+ * and the game ends when neither side has one (:435-457), so sign(score) is the
+ * game-theoretic win / draw / loss.  best = the lowest action index among the placements
+ * that achieve score, 64 (pass) whenever the side to move has no placement (terminal
+ * positions included).  Positions with more than max_empties empties or own & opp != 0 are
+ * not searched: score AZ_SOLVE_SKIPPED, best 255 (a caller may pass a whole sample buffer
+ * and read the mask back).  A search that visits more than node_limit nodes gives score
+ * AZ_SOLVE_ABORTED, best 255.  nodes_o (may be NULL): nodes visited per position.
+ * max_empties above AZ_SOLVE_MAX_EMPTIES is AZ_ERR_ARG. */
+#define AZ_SOLVE_SKIPPED (-128)
+#define AZ_SOLVE_ABORTED (-127)
+#define AZ_SOLVE_MAX_EMPTIES 14
+/* oth_solve_gpu's split front end expands roots with at least this many empties */
+#define AZ_SOLVE_SPLIT_MIN 9
+
+/* host pointers; reentrant and stateless */
+int oth_solve_cpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t max_empties,
+                  uint64_t node_limit, int8_t* score_o, uint8_t* best_o, uint64_t* nodes_o);
+/* device pointers, asynchronous on `stream`, n < 2^31.  The same search code as
+ * oth_solve_cpu, one lane per search: with split_plies = 0 nodes_o equals the host's.
+ * split_plies = 1 or 2 expands every root with at least AZ_SOLVE_SPLIT_MIN empties that many
+ * plies, solves the leaves as independent full-window searches and combines them: the same
+ * score and best, nodes_o = the sum over the leaves and expanded nodes, a root with an
+ * aborted leaf is aborted.  Call with workspace = NULL to get *workspace_bytes (a function
+ * of n, max_empties and split_plies; bounded: roots are processed in chunks), then again
+ * with that much 8-byte aligned device memory. */
+int oth_solve_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t max_empties,
+                  uint64_t node_limit, int32_t split_plies, int8_t* score_o, uint8_t* best_o,
+                  uint64_t* nodes_o, void* workspace, size_t* workspace_bytes, void* stream);
+
 /* ---------------- batched MCTS self-play engine (device) -------------------------
  * G game slots, each with its own flat SoA node arena (the reference's `Node` tree,
  * MCTS_model.py:46-169) in two ping-pong halves (live tree + re-root compaction target),
