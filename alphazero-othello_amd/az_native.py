@@ -31,6 +31,7 @@ AZ_FLAG_ILLEGAL = 4
 AZ_FLAG_PASSED = 8
 
 AZ_SOLVE_SKIPPED, AZ_SOLVE_ABORTED, AZ_SOLVE_MAX_EMPTIES = -128, -127, 14
+AZ_SEARCH_SKIPPED, AZ_SEARCH_ABORTED, AZ_SEARCH_MAX_DEPTH = -32768, -32767, 10
 
 AZ_EVAL_EXTERNAL, AZ_EVAL_ROLLOUT = 0, 1
 AZ_RNG_DEVICE, AZ_RNG_INJECTED = 0, 1
@@ -144,6 +145,10 @@ SIGNATURES = {
     "az_replay_aggregate_gpu": [_P] * 5 + [_I64] + [_P] * 10,
     "oth_solve_cpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
     "oth_solve_gpu": [_P, _P, _I64, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
+    "oth_eval_cpu": [_P, _P, _I64, _P],
+    "oth_eval_gpu": [_P, _P, _I64, _P, _P],
+    "oth_search_cpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
+    "oth_search_gpu": [_P, _P, _I64, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
 }
 
 
@@ -287,6 +292,26 @@ def solve_cpu(own, opp, max_empties=12, node_limit=1 << 31):
     check(lib.oth_solve_cpu(ptr(own), ptr(opp), own.size, int(max_empties), int(node_limit),
                             ptr(score), ptr(best), ptr(nodes)), "oth_solve_cpu")
     return score, best, nodes
+
+
+def eval_cpu(own, opp):
+    """Heuristic evaluation on the host: int16 per position (T(d) for terminal positions)."""
+    own, opp = _u64(own), _u64(opp)
+    value = np.empty(own.shape, np.int16)
+    check(lib.oth_eval_cpu(ptr(own), ptr(opp), own.size, ptr(value)), "oth_eval_cpu")
+    return value
+
+
+def search_cpu(own, opp, depth, node_limit=1 << 31):
+    """Depth-limited alpha-beta on the host: (value int16, best uint8, nodes uint64) per
+    position (AZ_SEARCH_SKIPPED / AZ_SEARCH_ABORTED in value for positions not searched)."""
+    own, opp = _u64(own), _u64(opp)
+    value = np.empty(own.shape, np.int16)
+    best = np.empty(own.shape, np.uint8)
+    nodes = np.empty(own.shape, np.uint64)
+    check(lib.oth_search_cpu(ptr(own), ptr(opp), own.size, int(depth), int(node_limit),
+                             ptr(value), ptr(best), ptr(nodes)), "oth_search_cpu")
+    return value, best, nodes
 
 
 def status_flags(st):

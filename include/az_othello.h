@@ -147,6 +147,50 @@ int oth_solve_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t m
                   uint64_t node_limit, int32_t split_plies, int8_t* score_o, uint8_t* best_o,
                   uint64_t* nodes_o, void* workspace, size_t* workspace_bytes, void* stream);
 
+/* ---------------- depth-limited alpha-beta with a heuristic evaluation ----------------
+ * Integer-only and identical on host and device (csrc/search.h).  own = side to move.
+ *   h(own, opp) = sum_sq W[sq] * ([sq in own] - [sq in opp])
+ *               + 12 * (popcount(legal(own, opp)) - popcount(legal(opp, own)))
+ * with W the classical D4-symmetric square table (rows 0..3, rows 4..7 mirror them):
+ *   100 -20  10   5   5  10 -20 100
+ *   -20 -50  -2  -2  -2  -2 -50 -20
+ *    10  -2  -1  -1  -1  -1  -2  10
+ *     5  -2  -1  -1  -1  -1  -2   5
+ * T(d) = sign(d) * (10000 + 100 * |d|), T(0) = 0, for d = popcount(own) - popcount(opp) of a
+ * position where neither side has a placement.  V(pos, depth), the first rule that matches:
+ * terminal -> T(d); depth 0 -> h; no placement -> -V(sides swapped, depth) (a pass costs no
+ * depth); else the maximum over placements of -V(child, depth - 1).
+ * oth_eval_*: T(d) for terminal positions, else h.
+ * oth_search_*: value = V(root, depth), best = the lowest action index among the placements
+ * that achieve it, 64 when the root has no placement (terminal roots included).  Positions
+ * with own & opp != 0 are not searched: value AZ_SEARCH_SKIPPED, best 255.  A search that
+ * visits more than node_limit nodes gives AZ_SEARCH_ABORTED, best 255.  nodes_o (may be
+ * NULL): nodes visited per position.  depth outside 1..AZ_SEARCH_MAX_DEPTH is AZ_ERR_ARG. */
+#define AZ_SEARCH_SKIPPED (-32768)
+#define AZ_SEARCH_ABORTED (-32767)
+#define AZ_SEARCH_MAX_DEPTH 10
+#define AZ_SEARCH_INF 32000 /* the full window; outside every value */
+
+/* host pointers; reentrant and stateless */
+int oth_eval_cpu(const uint64_t* own, const uint64_t* opp, int64_t n, int16_t* value_o);
+int oth_search_cpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t depth,
+                   uint64_t node_limit, int16_t* value_o, uint8_t* best_o, uint64_t* nodes_o);
+/* device pointers, asynchronous on `stream` */
+int oth_eval_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int16_t* value_o,
+                 void* stream);
+/* device pointers, asynchronous on `stream`, n < 2^31.  The same search code as
+ * oth_search_cpu, one lane per search: with split_plies = 0 nodes_o equals the host's.
+ * split_plies = 1 or 2 (and depth > split_plies; otherwise the call is unsplit) expands
+ * every non-terminal root that many plies, searches the leaves as independent full-window
+ * searches of the remaining depth (a pass child keeps its depth) and combines them: the same
+ * value and best, nodes_o = the sum over the leaves and expanded nodes, a root with an
+ * aborted leaf is aborted.  Call with workspace = NULL to get *workspace_bytes (a function
+ * of n, depth and split_plies; bounded: roots are processed in chunks), then again with
+ * that much 8-byte aligned device memory. */
+int oth_search_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t depth,
+                   uint64_t node_limit, int32_t split_plies, int16_t* value_o, uint8_t* best_o,
+                   uint64_t* nodes_o, void* workspace, size_t* workspace_bytes, void* stream);
+
 /* ---------------- batched MCTS self-play engine (device) -------------------------
  * G game slots, each with its own flat SoA node arena (the reference's `Node` tree,
  * MCTS_model.py:46-169) in two ping-pong halves (live tree + re-root compaction target),
