@@ -32,6 +32,8 @@ AZ_FLAG_PASSED = 8
 
 AZ_SOLVE_SKIPPED, AZ_SOLVE_ABORTED, AZ_SOLVE_MAX_EMPTIES = -128, -127, 14
 AZ_SEARCH_SKIPPED, AZ_SEARCH_ABORTED, AZ_SEARCH_MAX_DEPTH = -32768, -32767, 10
+AZ_REC_TERMINAL, AZ_REC_UNFINISHED, AZ_REC_ILLEGAL, AZ_REC_OVERFLOW = 0, 1, 2, 3
+AZ_REC_PASS_ROWS, AZ_REC_MAX_STRIDE, AZ_REC_MAX_ROWS = 1, 128, 128
 
 AZ_EVAL_EXTERNAL, AZ_EVAL_ROLLOUT = 0, 1
 AZ_RNG_DEVICE, AZ_RNG_INJECTED = 0, 1
@@ -149,6 +151,9 @@ SIGNATURES = {
     "oth_eval_gpu": [_P, _P, _I64, _P, _P],
     "oth_search_cpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
     "oth_search_gpu": [_P, _P, _I64, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
+    "oth_records_cpu": [_P, _I32, _P, _P, _P, _I64, _I32, _I32] + [_P] * 12,
+    "oth_records_gpu": [_P, _I32, _P, _P, _P, _I64, _I32, _I32] + [_P] * 12 + [_P],
+    "az_records_vote_gpu": [_P] * 4 + [_I64] + [_P] * 9,
 }
 
 

@@ -231,3 +231,207 @@ extern "C" int az_replay_aggregate_gpu(const uint64_t* own, const uint64_t* opp,
   AZ_HIP(hipGetLastError());
   return AZ_OK;
 }
+
+// ---- majority vote (az_records_vote_gpu) ------------------------------------------------
+// remove_conflicting_duplicates (supervised_benchmark.py:62-110) over bitboard rows:
+//   1. the stable sort and group numbering above, on (opp, own);
+//   2. per voted column (action, outcome): a second stable sort of the sorted rows by
+//      (group, value) makes every (group, value) a run whose rows are still in buffer order,
+//      so a run's length is the value's count and its first row the value's first appearance;
+//   3. every run head offers (count << 32) | ~first to its group by a 64-bit integer
+//      atomicMax: the most frequent value wins, a tie goes to the earlier first appearance,
+//      whatever order the offers arrive in.  A group receives one offer per distinct value
+//      (at most 65), so nothing depends on how many rows it has;
+//   4. groups emitted in order of first occurrence.
+namespace {
+
+__global__ void k_vote_heads(const uint64_t* __restrict__ own, const uint64_t* __restrict__ opp,
+                             const int32_t* __restrict__ idx, int32_t* __restrict__ head,
+                             int64_t n) {
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    int32_t h = 1;
+    if (j > 0) {
+      const int32_t a = idx[j], b = idx[j - 1];
+      h = own[a] != own[b] || opp[a] != opp[b];
+    }
+    head[j] = h;
+  }
+}
+
+// key of the second sort: (group number << 8) | (value + bias), through the board order
+__global__ void k_vote_keys(const int32_t* __restrict__ gid, const int32_t* __restrict__ idx,
+                            const uint8_t* __restrict__ val, int bias, uint64_t* __restrict__ key,
+                            uint64_t* __restrict__ best, int64_t n) {
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    const int v = bias ? (int)(int8_t)val[idx[j]] + bias : (int)val[idx[j]];
+    key[j] = ((uint64_t)(uint32_t)gid[j] << 8) | (uint64_t)(v & 0xFF);
+    best[j] = 0;
+  }
+}
+
+__global__ void k_run_heads(const uint64_t* __restrict__ key, int32_t* __restrict__ head,
+                            int64_t n) {
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n;
+       j += (int64_t)gridDim.x * blockDim.x)
+    head[j] = j == 0 || key[j] != key[j - 1];
+}
+
+// run r (1-based number rid[j] at its head) starts at sorted position rstart[r - 1]
+__global__ void k_run_starts(const int32_t* __restrict__ head, const int32_t* __restrict__ rid,
+                             int32_t* __restrict__ rstart, int64_t n) {
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    if (head[j]) rstart[rid[j] - 1] = (int32_t)j;
+    if (j == n - 1) rstart[rid[j]] = (int32_t)n;  // sentinel after the last run
+  }
+}
+
+__global__ void k_run_offer(const uint64_t* __restrict__ key, const int32_t* __restrict__ idx,
+                            const int32_t* __restrict__ head, const int32_t* __restrict__ rid,
+                            const int32_t* __restrict__ rstart, uint64_t* __restrict__ best,
+                            int64_t n) {
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    if (!head[j]) continue;
+    const uint32_t count = (uint32_t)(rstart[rid[j]] - (int32_t)j);
+    const uint32_t first = (uint32_t)idx[j];
+    const uint64_t group = (key[j] >> 8) - 1;  // < n
+    atomicMax(reinterpret_cast<unsigned long long*>(&best[group]),
+              ((unsigned long long)count << 32) | (0xFFFFFFFFu - first));
+  }
+}
+
+__global__ void k_vote_emit(const uint64_t* __restrict__ own, const uint64_t* __restrict__ opp,
+                            const uint8_t* __restrict__ act, const int8_t* __restrict__ z,
+                            const int32_t* __restrict__ idx, const int32_t* __restrict__ start,
+                            const int32_t* __restrict__ gorder,
+                            const uint64_t* __restrict__ best_a,
+                            const uint64_t* __restrict__ best_z,
+                            const int32_t* __restrict__ n_groups_p, uint64_t* __restrict__ own_o,
+                            uint64_t* __restrict__ opp_o, uint8_t* __restrict__ act_o,
+                            int8_t* __restrict__ z_o, int32_t* __restrict__ count_o) {
+  const int n_groups = *n_groups_p;
+  for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < n_groups;
+       o += gridDim.x * blockDim.x) {
+    const int g = gorder[o];
+    const int r0 = idx[start[g]];
+    own_o[o] = own[r0];
+    opp_o[o] = opp[r0];
+    act_o[o] = act[0xFFFFFFFFu - (uint32_t)best_a[g]];
+    z_o[o] = z[0xFFFFFFFFu - (uint32_t)best_z[g]];
+    count_o[o] = start[g + 1] - start[g];
+  }
+}
+
+}  // namespace
+
+extern "C" int az_records_vote_gpu(const uint64_t* own, const uint64_t* opp, const uint8_t* act,
+                                   const int8_t* z, int64_t n, uint64_t* own_o, uint64_t* opp_o,
+                                   uint8_t* act_o, int8_t* z_o, int32_t* count_o, int32_t* n_out,
+                                   void* workspace, size_t* workspace_bytes, void* stream) {
+  AZ_REQUIRE(n >= 0 && n < (int64_t(1) << 31) - 1, AZ_ERR_ARG,
+             "az_records_vote_gpu: n=%lld out of range", (long long)n);
+  AZ_REQUIRE(workspace_bytes, AZ_ERR_ARG, "az_records_vote_gpu: null workspace_bytes");
+  hipStream_t s = azc::as_stream(stream);
+  const int N = (int)(n > 0 ? n : 1);
+  constexpr int kKeyBits = 40;  // group number (< 2^31) << 8 | value
+  // workspace: idx x2, keys u64 x2, best u64 x2, head, gid, start, first x2, gnum x2,
+  // run head, run id, run start (N+1 each), cub temp
+  size_t cub_bytes = 0, t = 0;
+  AZ_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const uint64_t*)nullptr,
+                                            (uint64_t*)nullptr, (const int32_t*)nullptr,
+                                            (int32_t*)nullptr, N, 0, 64, s));
+  cub_bytes = t > cub_bytes ? t : cub_bytes;
+  AZ_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const uint64_t*)nullptr,
+                                            (uint64_t*)nullptr, (const int32_t*)nullptr,
+                                            (int32_t*)nullptr, N, 0, kKeyBits, s));
+  cub_bytes = t > cub_bytes ? t : cub_bytes;
+  AZ_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const int32_t*)nullptr,
+                                            (int32_t*)nullptr, (const int32_t*)nullptr,
+                                            (int32_t*)nullptr, N, 0, 32, s));
+  cub_bytes = t > cub_bytes ? t : cub_bytes;
+  AZ_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, t, (const int32_t*)nullptr,
+                                          (int32_t*)nullptr, N, s));
+  cub_bytes = t > cub_bytes ? t : cub_bytes;
+  const size_t i32 = align256((size_t)(N + 1) * 4), u64 = align256((size_t)N * 8);
+  const size_t need = 12 * i32 + 4 * u64 + align256(cub_bytes);
+  if (!workspace) {
+    *workspace_bytes = need;
+    return AZ_OK;
+  }
+  AZ_REQUIRE(*workspace_bytes >= need, AZ_ERR_ARG,
+             "az_records_vote_gpu: workspace %zu < %zu bytes", *workspace_bytes, need);
+  AZ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, AZ_ERR_ARG,
+             "az_records_vote_gpu: workspace must be 8-byte aligned");
+  AZ_REQUIRE(n_out, AZ_ERR_ARG, "az_records_vote_gpu: null n_out");
+  if (n == 0) {
+    AZ_HIP(hipMemsetAsync(n_out, 0, sizeof(int32_t), s));
+    return AZ_OK;
+  }
+  AZ_REQUIRE(own && opp && act && z && own_o && opp_o && act_o && z_o && count_o, AZ_ERR_ARG,
+             "az_records_vote_gpu: null buffer");
+  char* w = static_cast<char*>(workspace);
+  auto take = [&](size_t b) { char* p = w; w += b; return p; };
+  uint64_t* key_a = (uint64_t*)take(u64);
+  uint64_t* key_b = (uint64_t*)take(u64);
+  uint64_t* best_a = (uint64_t*)take(u64);
+  uint64_t* best_z = (uint64_t*)take(u64);
+  int32_t* idx_a = (int32_t*)take(i32);
+  int32_t* idx_b = (int32_t*)take(i32);
+  int32_t* head = (int32_t*)take(i32);
+  int32_t* gid = (int32_t*)take(i32);
+  int32_t* start = (int32_t*)take(i32);
+  int32_t* first_a = (int32_t*)take(i32);
+  int32_t* first_b = (int32_t*)take(i32);
+  int32_t* gnum_a = (int32_t*)take(i32);
+  int32_t* gnum_b = (int32_t*)take(i32);
+  int32_t* rhead = (int32_t*)take(i32);
+  int32_t* rid = (int32_t*)take(i32);
+  int32_t* rstart = (int32_t*)take(i32);
+  void* cub_tmp = take(align256(cub_bytes));
+  size_t cub_sz = cub_bytes;
+  const unsigned g = grid1(n);
+
+  // 1. stable LSD sort by opp, then own: the board order ends in idx_a
+  hipLaunchKernelGGL(k_iota, dim3(g), dim3(256), 0, s, idx_a, n);
+  hipLaunchKernelGGL(k_gather_u64, dim3(g), dim3(256), 0, s, opp, idx_a, key_a, n);
+  AZ_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_sz, key_a, key_b, idx_a, idx_b,
+                                            (int)n, 0, 64, s));
+  hipLaunchKernelGGL(k_gather_u64, dim3(g), dim3(256), 0, s, own, idx_b, key_a, n);
+  cub_sz = cub_bytes;
+  AZ_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_sz, key_a, key_b, idx_b, idx_a,
+                                            (int)n, 0, 64, s));
+  hipLaunchKernelGGL(k_vote_heads, dim3(g), dim3(256), 0, s, own, opp, idx_a, head, n);
+  cub_sz = cub_bytes;
+  AZ_HIP(hipcub::DeviceScan::InclusiveSum(cub_tmp, cub_sz, head, gid, (int)n, s));
+  hipLaunchKernelGGL(k_init_groups, dim3(g), dim3(256), 0, s, first_a, gnum_a, n);
+  hipLaunchKernelGGL(k_starts, dim3(g), dim3(256), 0, s, head, gid, idx_a, start, first_a,
+                     gnum_a, n);
+  AZ_HIP(hipMemcpyAsync(n_out, gid + (n - 1), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  // 2. + 3. the two votes (idx_b, key_b, rhead, rid, rstart are reused)
+  for (int col = 0; col < 2; ++col) {
+    const uint8_t* val = col == 0 ? act : reinterpret_cast<const uint8_t*>(z);
+    uint64_t* best = col == 0 ? best_a : best_z;
+    hipLaunchKernelGGL(k_vote_keys, dim3(g), dim3(256), 0, s, gid, idx_a, val, col == 0 ? 0 : 1,
+                       key_a, best, n);
+    cub_sz = cub_bytes;
+    AZ_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_sz, key_a, key_b, idx_a, idx_b,
+                                              (int)n, 0, kKeyBits, s));
+    hipLaunchKernelGGL(k_run_heads, dim3(g), dim3(256), 0, s, key_b, rhead, n);
+    cub_sz = cub_bytes;
+    AZ_HIP(hipcub::DeviceScan::InclusiveSum(cub_tmp, cub_sz, rhead, rid, (int)n, s));
+    hipLaunchKernelGGL(k_run_starts, dim3(g), dim3(256), 0, s, rhead, rid, rstart, n);
+    hipLaunchKernelGGL(k_run_offer, dim3(g), dim3(256), 0, s, key_b, idx_b, rhead, rid, rstart,
+                       best, n);
+  }
+  // 4. groups in order of first occurrence
+  cub_sz = cub_bytes;
+  AZ_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_sz, first_a, first_b, gnum_a, gnum_b,
+                                            (int)n, 0, 32, s));
+  hipLaunchKernelGGL(k_vote_emit, dim3(g), dim3(256), 0, s, own, opp, act, z, idx_a, start,
+                     gnum_b, best_a, best_z, n_out, own_o, opp_o, act_o, z_o, count_o);
+  AZ_HIP(hipGetLastError());
+  return AZ_OK;
+}

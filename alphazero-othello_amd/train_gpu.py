@@ -73,6 +73,40 @@ class DeviceReplayLoader:
         if seed is not None:
             self.gen.manual_seed(int(seed))
 
+    @classmethod
+    def from_bitboards(cls, own, opp, pi_or_act, v, batch_size, shuffle=True, augment=True,
+                       device=None, seed=None):
+        """A loader over rows that are already bitboards (records.replay / records.dedup,
+        the engine's sample rows): own / opp int64 bits (or NumPy uint64), v [n], and either
+        pi float [n, 65] or an action vector [n] (integer, 0..64), which becomes one-hot pi.
+        Device tensors stay where they are (device None = theirs)."""
+        def t(x, dt):
+            if not isinstance(x, torch.Tensor):
+                x = np.ascontiguousarray(x)
+                x = torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x)
+            return x.to(device=dev, dtype=dt).contiguous()
+
+        dev = torch.device(device) if device is not None else (
+            own.device if isinstance(own, torch.Tensor) else torch.device("cuda"))
+        self = cls.__new__(cls)
+        self.device = dev
+        self.own, self.opp = t(own, torch.int64).reshape(-1), t(opp, torch.int64).reshape(-1)
+        n = self.own.shape[0]
+        if pi_or_act.ndim == 1:
+            act = t(pi_or_act, torch.int64)
+            if n and (int(act.min()) < 0 or int(act.max()) > 64):
+                raise ValueError("from_bitboards: action outside 0..64")
+            self.pi = torch.zeros(n, 65, dtype=torch.float32, device=dev)
+            self.pi.scatter_(1, act[:, None], 1.0)
+        else:
+            self.pi = t(pi_or_act, torch.float32).reshape(n, 65)
+        self.v = t(v, torch.float32).reshape(n, 1)
+        self.batch_size, self.shuffle, self.aug = int(batch_size), shuffle, augment
+        self.gen = torch.Generator(device=dev)
+        if seed is not None:
+            self.gen.manual_seed(int(seed))
+        return self
+
     def __len__(self):
         return (self.own.shape[0] + self.batch_size - 1) // self.batch_size
 
@@ -114,3 +148,49 @@ def train_iters(policy, optimizer, loader, entropy_coef, value_loss=None):
         te += float(-e_loss.detach())
         nb += 1
     return tp / max(nb, 1), tv / max(nb, 1), te / max(nb, 1)
+
+
+def supervised_epoch(policy, optimizer, loader, value_loss=None):
+    """One epoch of the reference's supervised fit (supervised_benchmark.py:226-243
+    train_epoch) over device batches: cross-entropy on the move + MSE on the value, grad-norm
+    clip 1.0.  The policy term is -sum(pi * log_softmax) as in train_iters, which is
+    nn.CrossEntropyLoss for a one-hot pi and also takes the soft pi of dedup(how="mean").
+    Returns the mean total loss per batch."""
+    value_loss = value_loss or nn.MSELoss()
+    policy.train()
+    total = 0.0
+    nb = 0
+    for state, target_pi, target_v in loader:
+        logits, value = policy(state)
+        p_loss = -torch.mean(torch.sum(target_pi * F.log_softmax(logits, dim=-1), dim=-1))
+        loss = p_loss + value_loss(value, target_v)
+        optimizer.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(policy.parameters(), 1.0)
+        optimizer.step()
+        total += float(loss.detach())
+        nb += 1
+    return total / max(nb, 1)
+
+
+@torch.no_grad()
+def supervised_eval(policy, loader, value_loss=None):
+    """The reference's evaluate (supervised_benchmark.py:246-275): mean total, policy and
+    value loss per batch and the top-1 move accuracy (argmax of the logits against argmax of
+    the target pi) over the loader's rows."""
+    value_loss = value_loss or nn.MSELoss()
+    policy.eval()
+    tl = tp = tv = 0.0
+    nb = correct = rows = 0
+    for state, target_pi, target_v in loader:
+        logits, value = policy(state)
+        p_loss = -torch.mean(torch.sum(target_pi * F.log_softmax(logits, dim=-1), dim=-1))
+        v_loss = value_loss(value, target_v)
+        tl += float(p_loss + v_loss)
+        tp += float(p_loss)
+        tv += float(v_loss)
+        correct += int((logits.argmax(dim=1) == target_pi.argmax(dim=1)).sum())
+        rows += int(state.shape[0])
+        nb += 1
+    nb = max(nb, 1)
+    return tl / nb, tp / nb, tv / nb, correct / max(rows, 1)

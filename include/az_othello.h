@@ -612,6 +612,78 @@ int az_replay_aggregate_gpu(const uint64_t* own, const uint64_t* opp, const int3
                             int32_t* count_o, int32_t* n_out, void* workspace,
                             size_t* workspace_bytes, void* stream);
 
+/* ---------------- game records -> training rows ---------------------------------------
+ * process_game of the reference's supervised data path (supervised_benchmark.py:113-223)
+ * for a batch of recorded games, on bitboards and with the true side to move: the reference
+ * alternates colours blindly, so every row after a pass it was not told about carries the
+ * wrong mover and the wrong sign on its value; here a pass the record omits is inserted.
+ *
+ * acts: uint8 [n][stride], stride a multiple of 16 and at most AZ_REC_MAX_STRIDE, base
+ * 16-byte aligned.  Entry 0..63 = placement at row*8+col, 64 = pass, 255 = end of the game
+ * (a line without a 255 has stride entries).  own0 / opp0 [n]: start positions, own = the
+ * first mover (colour +1); both NULL = the initial position.  winner int8 [n] in
+ * {+1, 0, -1} from the first mover's view, or NULL.
+ *
+ * Per game, entry by entry, with (own, opp, colour) the side to move:
+ *   placement a: if the mover has no placement, the opponent has one and a is legal for the
+ *     opponent, a forced pass is played first (sides swapped, colour flipped, one ply
+ *     counted; a row with action 64 only under AZ_REC_PASS_ROWS).  Then a must be legal for
+ *     the mover: the row (own, opp, a) is emitted and the board stepped.
+ *   64: legal only when the mover has no placement and the opponent has one; a row only
+ *     under AZ_REC_PASS_ROWS; sides swapped.
+ * A placement on an occupied square or one that flips nothing, an entry in 65..254, a pass
+ * while a placement exists and any entry after the position is terminal stop the game with
+ * status AZ_REC_ILLEGAL and bad_ply = the entry's index; a row past max_rows (<= 128) stops
+ * it with AZ_REC_OVERFLOW (bad_ply = the entry's index as well); the rows emitted before
+ * stay.  Otherwise status = AZ_REC_TERMINAL when neither side has a placement at the end of
+ * the line, AZ_REC_UNFINISHED when one has, and bad_ply = 255.
+ *
+ * Rows are ply-major: row r of game g is at index r*n + g of own_o / opp_o (canonical, the
+ * mover as own), act_o, z_o (winner x the mover's colour) and ply_o (the ply of the game:
+ * the entry's index plus the forced passes inserted before it -- what keep_by_ply keys on;
+ * identical for a record with and without its passes written out).  Rows r >= n_rows[g] are
+ * not written.  Per game: n_rows, status, bad_ply, the position the replay stopped at
+ * (final_own / final_opp with final_colour to move) and final_diff, its disc difference
+ * from the first mover's view.  With winner NULL, z uses sign(final_diff) for terminal games
+ * and 0 for the others; a winner given is used as it is.
+ * n = 0 is AZ_OK; null or misaligned required pointers are AZ_ERR_ARG. */
+#define AZ_REC_TERMINAL 0
+#define AZ_REC_UNFINISHED 1
+#define AZ_REC_ILLEGAL 2
+#define AZ_REC_OVERFLOW 3
+#define AZ_REC_PASS_ROWS 1 /* flags bit: passes (written or inserted) emit rows too */
+#define AZ_REC_MAX_STRIDE 128
+#define AZ_REC_MAX_ROWS 128
+
+/* host pointers; reentrant and stateless */
+int oth_records_cpu(const uint8_t* acts, int32_t stride, const uint64_t* own0,
+                    const uint64_t* opp0, const int8_t* winner, int64_t n, int32_t max_rows,
+                    int32_t flags, uint64_t* own_o, uint64_t* opp_o, uint8_t* act_o, int8_t* z_o,
+                    uint8_t* ply_o, int32_t* n_rows, uint8_t* status, uint8_t* bad_ply,
+                    uint64_t* final_own, uint64_t* final_opp, int8_t* final_colour,
+                    int8_t* final_diff);
+/* device pointers, asynchronous on `stream`, n * max_rows < 2^31.  The same replay code as
+ * oth_records_cpu (csrc/records.h), one lane per game: bit-identical outputs. */
+int oth_records_gpu(const uint8_t* acts, int32_t stride, const uint64_t* own0,
+                    const uint64_t* opp0, const int8_t* winner, int64_t n, int32_t max_rows,
+                    int32_t flags, uint64_t* own_o, uint64_t* opp_o, uint8_t* act_o, int8_t* z_o,
+                    uint8_t* ply_o, int32_t* n_rows, uint8_t* status, uint8_t* bad_ply,
+                    uint64_t* final_own, uint64_t* final_opp, int8_t* final_colour,
+                    int8_t* final_diff, void* stream);
+
+/* remove_conflicting_duplicates (supervised_benchmark.py:62-110) on bitboard rows (device):
+ * one output row per distinct (own, opp), in order of first occurrence; act_o = the group's
+ * most frequent action, z_o = its most frequent outcome, a tie going to the value that
+ * appeared first in buffer order (Counter.most_common(1)); count_o = group size; *n_out
+ * (device int32) = number of groups.  Inputs own / opp [n], act uint8 [n], z int8 [n];
+ * outputs sized n.  Deterministic, and the work per row does not depend on the size of its
+ * group.  Call with workspace = NULL to get *workspace_bytes, then again with that much
+ * device memory.  Asynchronous on `stream`. */
+int az_records_vote_gpu(const uint64_t* own, const uint64_t* opp, const uint8_t* act,
+                        const int8_t* z, int64_t n, uint64_t* own_o, uint64_t* opp_o,
+                        uint8_t* act_o, int8_t* z_o, int32_t* count_o, int32_t* n_out,
+                        void* workspace, size_t* workspace_bytes, void* stream);
+
 /* AlphaZeroNet's policy and value heads in one kernel (reference Models.py:196-221 with
  * BatchNorm folded, softmax of MCTS_model.py:319): h NHWC float [n_boards, 8, 8, C];
  * wpv [3][C] (rows: policy ch 0, policy ch 1, value) and bpv [3] the 1x1 convs; wpolT
