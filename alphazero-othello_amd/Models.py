@@ -405,6 +405,18 @@ def board_absmax(x, out=None):
     return out
 
 
+FP16X2_SCALE_EXP_MIN = -100  # csrc/common.h: AZ_SCALE_EXP_MIN
+
+
+def fp16x2_scale_exp(max_abs) -> int:
+    """The FP16X2 scale exponent of a max |x| (a 0-dim float32 tensor), as the kernels take it
+    (az_scale_exp, csrc/common.h): frexp's e (max < 2^e), never below FP16X2_SCALE_EXP_MIN, so
+    that the scale 2^(15 - e) and the sum of two such exponents the epilogue removes stay
+    inside fp32's range; 0 -> 0."""
+    e = int(torch.frexp(max_abs.float())[1].item())
+    return max(e, FP16X2_SCALE_EXP_MIN) if float(max_abs) > 0 else 0
+
+
 def _merge_1x1(a: nn.Conv2d, b: nn.Conv2d) -> nn.Conv2d:
     m = nn.Conv2d(a.in_channels, a.out_channels + b.out_channels, 1)
     m.weight = nn.Parameter(torch.cat([a.weight.detach(), b.weight.detach()], 0))
@@ -858,7 +870,7 @@ class FusedInferenceNet(nn.Module, Inference):
                 # |W| < 2^(15 - wshift)) and split into fp16 hi / lo planes laid out as the MFMA
                 # B fragments [K/16][hi, lo][128][16]; column 128 stays fp32 (its FMAs)
                 w128 = wt[:, :128]
-                e = int(torch.frexp(w128.abs().max())[1].item())  # max |W| < 2^e
+                e = fp16x2_scale_exp(w128.abs().max())  # max |W| < 2^e
                 ws = w128 * (2.0 ** (15 - e))  # exact: a power of two
                 hi = ws.half()
                 lo = (ws - hi.float()).half()

@@ -351,8 +351,7 @@ __global__ __launch_bounds__(G::THREADS) void k_conv3x3_mx(const float* __restri
       __syncthreads();
 #pragma unroll
       for (int b = 0; b < kBoards; ++b) {
-        const unsigned mb = s_amax[b];
-        const int be = (int)((mb >> 23) & 0xff), e = be == 0 ? 0 : be - 126;  // max < 2^e
+        const int e = az_scale_exp(s_amax[b]);  // max < 2^e
         xsc[b] = ldexpf(1.0f, 15 - e);
       }
     }
@@ -425,8 +424,7 @@ __global__ __launch_bounds__(G::THREADS) void k_conv3x3_mx(const float* __restri
     const int sw = reinterpret_cast<const int*>(wq + G::W_BYTES)[1];
 #pragma unroll
     for (int mi = 0; mi < G::TM; ++mi) {
-      const unsigned mb = s_amax[(32 * mi) >> 6];
-      const int be = (int)((mb >> 23) & 0xff), e = be == 0 ? 0 : be - 126;
+      const int e = az_scale_exp(s_amax[(32 * mi) >> 6]);
       osc[mi] = ldexpf(1.0f, -(15 - e) - sw);
     }
   }
@@ -567,8 +565,7 @@ __global__ __launch_bounds__(G::THREADS) AZ_FT_ATTR void k_fast_trunk(FastTrunkA
     unsigned mb = s_amax[0];
 #pragma unroll
     for (int w = 1; w < G::WAVES; ++w) mb = max(mb, s_amax[w]);
-    const int be = (int)((mb >> 23) & 0xff);
-    e_in = be == 0 ? 0 : be - 126;
+    e_in = az_scale_exp(mb);
     const float xsc = ldexpf(1.0f, 15 - e_in);
 #pragma unroll
     for (int i = 0; i < ITER; ++i) {
@@ -662,8 +659,7 @@ __global__ __launch_bounds__(G::THREADS) AZ_FT_ATTR void k_fast_trunk(FastTrunkA
     unsigned mb = s_amax[0];
 #pragma unroll
     for (int w = 1; w < G::WAVES; ++w) mb = max(mb, s_amax[w]);
-    const int be = (int)((mb >> 23) & 0xff);
-    e_in = be == 0 ? 0 : be - 126;
+    e_in = az_scale_exp(mb);
     const float xsc = ldexpf(1.0f, 15 - e_in);
 #pragma unroll
     for (int mi = 0; mi < G::TM; ++mi)
@@ -695,8 +691,7 @@ __global__ void k_conv_mx_prep(const float* __restrict__ w9, uint16_t* __restric
   const int n = 9 * C * C;
   float wsc = 1.0f;
   if constexpr (MODE == AZ_CONV_FP16X2 && !MAXPASS) {
-    const unsigned mb = hdr[0];  // max |w| < 2^e
-    const int be = (int)((mb >> 23) & 0xff), e = be == 0 ? 0 : be - 126;
+    const int e = az_scale_exp(hdr[0]);  // max |w| < 2^e
     wsc = ldexpf(1.0f, 15 - e);  // scaled max < 2^15
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr[1] = (unsigned)(15 - e);
   }

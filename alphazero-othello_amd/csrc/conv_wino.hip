@@ -523,8 +523,7 @@ __global__ void k_wino_prep(const float* __restrict__ w9, uint16_t* __restrict__
   const int n = C * C;
   float usc = 1.0f;
   if constexpr (MODE == AZ_CONV_FP16X2 && !MAXPASS) {
-    const unsigned mb = hdr[0];  // max |U| bits: max |U| < 2^e (frexp's exponent)
-    const int be = (int)((mb >> 23) & 0xff), e = be == 0 ? 0 : be - 126;
+    const int e = az_scale_exp(hdr[0]);  // max |U| bits: max |U| < 2^e (frexp's exponent)
     usc = ldexpf(1.0f, 15 - e);           // scaled max < 2^15 (fp16 max 65504)
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr[1] = (unsigned)(15 - e);
   }

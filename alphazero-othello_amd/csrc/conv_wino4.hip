@@ -294,11 +294,9 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// frexp's exponent of a non-negative finite float (x < 2^e; 0 -> 0), from its bits
-__device__ __forceinline__ int frexp_exp(float x) {
-  const int b = (int)((__float_as_uint(x) >> 23) & 0xff);
-  return b == 0 ? (x > 0.0f ? -125 : 0) : b - 126;
-}
+// frexp's exponent of a non-negative finite float (x < 2^e; 0 -> 0), clamped below as every
+// FP16X2 scale exponent is (az_scale_exp, common.h)
+__device__ __forceinline__ int frexp_exp(float x) { return az_scale_exp(__float_as_uint(x)); }
 
 // window rows of group k: B^T row k = sa * d_a0 + sb * d_a1 (B^T = [1 0 -1 0; 0 1 1 0;
 // 0 -1 1 0; 0 1 0 -1]); multiplying by +-1 is exact, so this is the transform's own

@@ -283,8 +283,7 @@ __global__ __launch_bounds__(256) void k_heads_fast_gemm(const float* __restrict
 #pragma unroll
   for (int j = 0; j < R; ++j) {
     const int row = row0 + 32 * j;
-    const unsigned mb = s_max[row];
-    const int be = (int)((mb >> 23) & 0xff), e = be == 0 ? 0 : be - 126;  // max < 2^e
+    const int e = az_scale_exp(s_max[row]);  // max < 2^e
     const float sc = ldexpf(1.0f, 15 - e);
 #pragma unroll
     for (int i = 0; i < G::ITER; ++i) {
@@ -328,8 +327,7 @@ __global__ __launch_bounds__(256) void k_heads_fast_gemm(const float* __restrict
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const int row = 32 * t + (k & 3) + 8 * (k >> 2) + 4 * h, b = b0 + row;
-      const unsigned mb = s_max[row];
-      const int be = (int)((mb >> 23) & 0xff), e = be == 0 ? 0 : be - 126;
+      const int e = az_scale_exp(s_max[row]);
       if (b < n_boards) out[(size_t)b * ld + col] = acc[t][k] * ldexpf(1.0f, -(15 - e) - wshift);
     }
   if (tid < G::ROWS && b0 + tid < n_boards) {  // column 128 (fp32 FMAs), columns past it zero
