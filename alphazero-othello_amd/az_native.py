@@ -31,6 +31,7 @@ AZ_FLAG_ILLEGAL = 4
 AZ_FLAG_PASSED = 8
 
 AZ_SOLVE_SKIPPED, AZ_SOLVE_ABORTED, AZ_SOLVE_MAX_EMPTIES = -128, -127, 14
+AZ_SOLVE_DEEP_MAX_EMPTIES = 20
 AZ_SEARCH_SKIPPED, AZ_SEARCH_ABORTED, AZ_SEARCH_MAX_DEPTH = -32768, -32767, 10
 AZ_REC_TERMINAL, AZ_REC_UNFINISHED, AZ_REC_ILLEGAL, AZ_REC_OVERFLOW = 0, 1, 2, 3
 AZ_REC_PASS_ROWS, AZ_REC_MAX_STRIDE, AZ_REC_MAX_ROWS = 1, 128, 128
@@ -147,6 +148,8 @@ SIGNATURES = {
     "az_replay_aggregate_gpu": [_P] * 5 + [_I64] + [_P] * 10,
     "oth_solve_cpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
     "oth_solve_gpu": [_P, _P, _I64, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
+    "oth_solve_deep_cpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _P, _P, _P],
+    "oth_solve_deep_gpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
     "oth_eval_cpu": [_P, _P, _I64, _P],
     "oth_eval_gpu": [_P, _P, _I64, _P, _P],
     "oth_search_cpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
@@ -296,6 +299,46 @@ def solve_cpu(own, opp, max_empties=12, node_limit=1 << 31):
     nodes = np.empty(own.shape, np.uint64)
     check(lib.oth_solve_cpu(ptr(own), ptr(opp), own.size, int(max_empties), int(node_limit),
                             ptr(score), ptr(best), ptr(nodes)), "oth_solve_cpu")
+    return score, best, nodes
+
+
+def solve_deep_cpu(own, opp, max_empties=16, alpha=-65, beta=65, node_limit=1 << 31):
+    """Windowed, move-ordered endgame solve on the host (up to AZ_SOLVE_DEEP_MAX_EMPTIES
+    empties): (score int8, best uint8, nodes uint64) per position; score is exact inside
+    (alpha, beta) and a bound on the true score outside it."""
+    own, opp = _u64(own), _u64(opp)
+    score = np.empty(own.shape, np.int8)
+    best = np.empty(own.shape, np.uint8)
+    nodes = np.empty(own.shape, np.uint64)
+    check(lib.oth_solve_deep_cpu(ptr(own), ptr(opp), own.size, int(max_empties), int(alpha),
+                                 int(beta), int(node_limit), ptr(score), ptr(best), ptr(nodes)),
+          "oth_solve_deep_cpu")
+    return score, best, nodes
+
+
+def solve_deep_gpu(own, opp, max_empties=16, alpha=-65, beta=65, node_limit=1 << 31,
+                   split_plies=0, stream=None):
+    """oth_solve_deep_gpu on int64 device tensors (the uint64 bitboards' bits), asynchronous
+    on `stream` (default: the current stream).  Returns device tensors (score int8, best
+    uint8, nodes int64 = the uint64 counts' bits)."""
+    import torch
+
+    dev = own.device
+    n = own.numel()
+    score = torch.empty(n, dtype=torch.int8, device=dev)
+    best = torch.empty(n, dtype=torch.uint8, device=dev)
+    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    need = ctypes.c_size_t(0)
+    args = (int(max_empties), int(alpha), int(beta), int(node_limit), int(split_plies))
+    check(lib.oth_solve_deep_gpu(None, None, n, *args, None, None, None, None,
+                                 ctypes.byref(need), None), "oth_solve_deep_gpu")
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            ws = torch.empty(max(need.value, 8), dtype=torch.uint8, device=dev)
+            check(lib.oth_solve_deep_gpu(ptr(own), ptr(opp), n, *args, ptr(score), ptr(best),
+                                         ptr(nodes), ptr(ws), ctypes.byref(need),
+                                         stream_ptr(s)), "oth_solve_deep_gpu")
     return score, best, nodes
 
 

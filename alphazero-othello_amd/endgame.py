@@ -10,6 +10,10 @@ host (oth_solve_cpu over a thread pool; ctypes releases the GIL).  On top of it:
   how often it is optimal, how often it keeps the win / draw / loss, how many discs it gives
   away.
 
+`solve_deep` is a second solver beside it (csrc/solve_deep.h): a root window ("wld" = (-1, 1)
+gives the exact win / draw / loss for a fraction of the nodes) and ordered moves, up to 20
+empties; `relabel_rows(wld=True)` and `move_report` beyond 14 empties go through it.
+
 score = final own - opp disc difference from the side to move's view (the reference's plain
 count, envs/othello.py:214-220), best = the lowest optimal action (64 = pass).
 """
@@ -66,6 +70,33 @@ def _solve_cpu(own, opp, max_empties, node_limit):
             rcs = list(ex.map(run, bounds))
     for rc in rcs:
         nat.check(rc, "oth_solve_cpu")
+    return score, best, nodes
+
+
+def _solve_deep_cpu(own, opp, max_empties, alpha, beta, node_limit):
+    """oth_solve_deep_cpu over the same thread pool as _solve_cpu."""
+    n = own.size
+    score, best = np.empty(n, np.int8), np.empty(n, np.uint8)
+    nodes = np.empty(n, np.uint64)
+    window = (int(alpha), int(beta), int(node_limit))
+
+    def run(ab):
+        a, b = ab
+        return nat.lib.oth_solve_deep_cpu(nat.ptr(own[a:b]), nat.ptr(opp[a:b]), b - a,
+                                          int(max_empties), *window, nat.ptr(score[a:b]),
+                                          nat.ptr(best[a:b]), nat.ptr(nodes[a:b]))
+
+    threads = min(MAX_THREADS, n)
+    if threads <= 1 or not 0 <= max_empties <= nat.AZ_SOLVE_DEEP_MAX_EMPTIES \
+            or not -65 <= alpha < beta <= 65:
+        # one call: the library validates the arguments (and accepts n = 0)
+        nat.check(run((0, n)), "oth_solve_deep_cpu")
+        return score, best, nodes
+    size = max(1, min(256, n // (threads * 8) or 1))  # interleaved, as in _solve_cpu
+    with ThreadPoolExecutor(threads) as ex:
+        rcs = list(ex.map(run, [(a, min(n, a + size)) for a in range(0, n, size)]))
+    for rc in rcs:
+        nat.check(rc, "oth_solve_deep_cpu")
     return score, best, nodes
 
 
@@ -144,25 +175,79 @@ def solve(own, opp, max_empties=12, device=None, node_limit=1 << 31, split_plies
     return s, b, nd
 
 
+# fastest on the 1..12-empties corpus workload with the full window (scripts/bench_solve_deep.py,
+# profiles/solve_deep_bench.json: 0.88 s against 0.90 s unsplit and 2.23 s at two plies) and
+# level with split 0 in (-1, 1) (0.264 / 0.250 / 0.790 s, inside the repeats' spread).  Two
+# plies win when every root is hard (256 roots at 14 / 16 empties in (-1, 1): 0.40 / 3.5 s
+# against 0.71 / 4.5 s).
+DEFAULT_DEEP_SPLIT_PLIES = 1
+
+
+def _window(window):
+    if window is None:
+        return -65, 65
+    if isinstance(window, str):
+        if window != "wld":
+            raise ValueError(f"window={window!r}: None, 'wld' or (alpha, beta)")
+        return -1, 1
+    alpha, beta = window
+    return int(alpha), int(beta)
+
+
+def solve_deep(own, opp, max_empties=16, window=None, device=None, node_limit=1 << 31,
+               split_plies=None):
+    """Windowed, move-ordered solve (csrc/solve_deep.h) of every position with at most
+    `max_empties` <= 20 empties: returns (score, best, nodes) with `solve`'s array / tensor
+    conventions, device choice, host thread pool and skipped / aborted codes.
+
+    window None = the full window: score is exact and best an optimal action (not
+    necessarily the lowest).  "wld" = (-1, 1): sign(score) is the exact win / draw / loss,
+    score itself only a bound.  (alpha, beta): score is exact inside the window, else a
+    bound on the true score on the same side of it (see include/az_othello.h).
+    split_plies (GPU only) None = DEFAULT_DEEP_SPLIT_PLIES."""
+    alpha, beta = _window(window)
+    want_torch = isinstance(own, torch.Tensor)
+    dev = _pick_device(device, own, opp)
+    if dev.type == "cuda":
+        sp = DEFAULT_DEEP_SPLIT_PLIES if split_plies is None else int(split_plies)
+        s, b, nd = nat.solve_deep_gpu(_as_i64_tensor(own, dev), _as_i64_tensor(opp, dev),
+                                      max_empties, alpha, beta, node_limit, sp)
+        if want_torch:
+            return s, b, nd
+        return s.cpu().numpy(), b.cpu().numpy(), nd.cpu().numpy().view(np.uint64)
+    s, b, nd = _solve_deep_cpu(_as_u64_numpy(own), _as_u64_numpy(opp), max_empties, alpha, beta,
+                               node_limit)
+    if want_torch:
+        return (torch.from_numpy(s).to(own.device), torch.from_numpy(b).to(own.device),
+                torch.from_numpy(nd.view(np.int64)).to(own.device))
+    return s, b, nd
+
+
 def _check_solved(score, what):
     if (score == nat.AZ_SOLVE_ABORTED).any():
         raise RuntimeError(f"{what}: {int((score == nat.AZ_SOLVE_ABORTED).sum())} searches "
                            "exceeded the node limit")
 
 
-def relabel_rows(rows, max_empties, device=None):
+def relabel_rows(rows, max_empties, device=None, wld=False):
     """Exact value targets: in engine sample rows (dict of own / opp / pi / z / player, z
     already from the side to move's view: canonical rows) replace z by float(sign(score)) for
     every row whose position has 1..max_empties empties; other rows and fields are untouched.
     Returns (rows, mask) with mask the boolean array of relabelled rows; `rows` is a new
-    dict sharing every array but z."""
+    dict sharing every array but z.  wld=True takes the sign from solve_deep's (-1, 1)
+    window instead of the exact disc count: the same labels for fewer nodes, and max_empties
+    up to 20."""
     own, opp = _as_u64_numpy(rows["own"]), _as_u64_numpy(rows["opp"])
     e = empties(own, opp)
     mask = (e >= 1) & (e <= int(max_empties)) & ((own & opp) == 0)
     out = dict(rows)
     z = np.array(np.asarray(rows["z"]), dtype=np.float64, copy=True)
     if mask.any():
-        score, _, _ = solve(own[mask], opp[mask], max_empties, device=device)
+        if wld:
+            score, _, _ = solve_deep(own[mask], opp[mask], max_empties, window="wld",
+                                     device=device)
+        else:
+            score, _, _ = solve(own[mask], opp[mask], max_empties, device=device)
         _check_solved(score, "relabel_rows")
         z[mask] = np.sign(score.astype(np.int64)).astype(np.float64)
     out["z"] = z
@@ -185,7 +270,8 @@ def move_report(rows, max_empties, device=None):
     move), compared with the position's own exact score; roots and children are solved in
     one batch.  Returns {"by_empties": {e: stats}, "total": stats} with stats = n,
     optimal_frac (value of a == score), wld_kept_frac (same sign) and mean_disc_loss
-    (score - value of a, in discs)."""
+    (score - value of a, in discs).  max_empties up to 14 is solved by `solve`, 15..20 by
+    `solve_deep` with the full window."""
     own, opp = _as_u64_numpy(rows["own"]), _as_u64_numpy(rows["opp"])
     e = empties(own, opp)
     mask = (e >= 1) & (e <= int(max_empties)) & ((own & opp) == 0)
@@ -194,8 +280,9 @@ def move_report(rows, max_empties, device=None):
     act = pi.argmax(axis=1).astype(np.uint8)
     cown, copp, _, _ = nat.step_cpu(own, opp, act)
     n = len(own)
-    score, _, _ = solve(np.concatenate([own, cown]), np.concatenate([opp, copp]), max_empties,
-                        device=device)
+    deep = int(max_empties) > nat.AZ_SOLVE_MAX_EMPTIES  # 15..20: solve_deep, full window
+    score, _, _ = (solve_deep if deep else solve)(
+        np.concatenate([own, cown]), np.concatenate([opp, copp]), max_empties, device=device)
     _check_solved(score, "move_report")
     score = score.astype(np.int64)
     root, value = score[:n], -score[n:]

@@ -369,7 +369,14 @@ def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, strea
     game-theoretic target z = sign(score) from the endgame solver (endgame.relabel_rows, on
     each rank's own rows before the all-gather) instead of the played game's outcome.  Only
     those rows change: with lambda < 1 the earlier rows keep their TD(lambda) targets, which
-    were built from the played outcome.  0 (the default) leaves the rows as they are."""
+    were built from the played outcome.  0 (the default) leaves the rows as they are.  E up
+    to 14 goes through the exact solver; E in 15..20 through the windowed, move-ordered one in
+    win / draw / loss mode (endgame.relabel_rows(wld=True)), which yields the same sign.
+    The labelling runs on the rank's GPU when there is one, at endgame's default split.  On
+    a few hundred roots of 15..20 empties that is several times slower than 16 host threads
+    (the windowed solver's measured table); a caller to whom that matters keeps
+    exact_endgame <= 14 here and labels engine sample rows itself with
+    endgame.relabel_rows(rows, E, device="cpu", wld=True)."""
     import torch.distributed as dist
 
     distributed = dist.is_available() and dist.is_initialized() and \
@@ -401,7 +408,9 @@ def _exact_rows(rows, exact_endgame):
         return rows
     from endgame import relabel_rows
 
-    return relabel_rows(rows, exact_endgame)[0]
+    from az_native import AZ_SOLVE_MAX_EMPTIES
+
+    return relabel_rows(rows, exact_endgame, wld=exact_endgame > AZ_SOLVE_MAX_EMPTIES)[0]
 
 
 def _collective_device(group=None):

@@ -147,6 +147,37 @@ int oth_solve_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t m
                   uint64_t node_limit, int32_t split_plies, int8_t* score_o, uint8_t* best_o,
                   uint64_t* nodes_o, void* workspace, size_t* workspace_bytes, void* stream);
 
+/* ---------------- windowed, move-ordered endgame solver ------------------------------
+ * A second solver beside oth_solve_* (csrc/solve_deep.h): the same values and conventions
+ * (score from the side to move's view, AZ_SOLVE_SKIPPED / AZ_SOLVE_ABORTED with best 255,
+ * nodes_o may be NULL and counts the positions entered, not the ordering probes), with a
+ * root window and ordered moves, up to AZ_SOLVE_DEEP_MAX_EMPTIES empties.
+ * The root is searched in (alpha, beta), -65 <= alpha < beta <= 65 (anything else is
+ * AZ_ERR_ARG); (-65, 65) is the full window.  With s the true score, the score v returned is
+ *   v = s             if alpha < s < beta,
+ *   beta <= v <= s    if s >= beta,
+ *   s <= v <= alpha   if s <= alpha,
+ * so sign(v) under (-1, 1) is the exact win / draw / loss.  best: an optimal action when
+ * alpha < v < beta (not necessarily the lowest one), an action worth at least beta when
+ * v >= beta, some legal action when v <= alpha; 64 whenever the side to move has no
+ * placement. */
+#define AZ_SOLVE_DEEP_MAX_EMPTIES 20
+/* host pointers; reentrant and stateless */
+int oth_solve_deep_cpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t max_empties,
+                       int32_t alpha, int32_t beta, uint64_t node_limit, int8_t* score_o,
+                       uint8_t* best_o, uint64_t* nodes_o);
+/* device pointers, asynchronous on `stream`, n < 2^31; workspace protocol as oth_solve_gpu.
+ * split_plies = 0: score, best and nodes_o equal the host's.  split_plies = 1 or 2 expands
+ * every root with at least AZ_SOLVE_SPLIT_MIN empties that many plies, solves the leaves in
+ * the windows the root's window implies and combines them: scores within the contract
+ * above (equal to the host's with the full window), best within it (the lowest action among
+ * the best), nodes_o = the sum over the leaves and expanded nodes (more than the host's:
+ * siblings do not narrow each other's windows), a root with an aborted leaf is aborted. */
+int oth_solve_deep_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t max_empties,
+                       int32_t alpha, int32_t beta, uint64_t node_limit, int32_t split_plies,
+                       int8_t* score_o, uint8_t* best_o, uint64_t* nodes_o, void* workspace,
+                       size_t* workspace_bytes, void* stream);
+
 /* ---------------- depth-limited alpha-beta with a heuristic evaluation ----------------
  * Integer-only and identical on host and device (csrc/search.h).  own = side to move.
  *   h(own, opp) = sum_sq W[sq] * ([sq in own] - [sq in opp])
