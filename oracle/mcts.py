@@ -23,6 +23,13 @@ at once; one reaching an unexpanded leaf waits (its virtual loss stays) until K 
 simulations are all started; the waiting ones then finish in start order (expand once per
 distinct leaf, back up each one's value).
 
+node_capacity = C restates the one rule the engine adds to the reference (engine.hip
+expand_backup_leaf): a leaf whose children would not fit in the C-node arena (nodes in the
+tree + its legal actions > C) is evaluated and its value backed up, but it gets no children
+and `overflows` counts it -- once per expansion skipped, so once for a leaf several descents
+of one K-leaf batch wait on.  The leaf stays unexpanded and may be chosen again.  make_move
+compacts the tree, so the count of nodes in use drops with every re-root.
+
 RNG draws go through an adapter so a test can either replay the reference's global
 np.random stream call-for-call (NumpyRng) or inject recorded draws (LogRng).
 """
@@ -98,8 +105,13 @@ class SeqMCTS:
     """Flat-array tree; node 0 is the root after every re-root."""
 
     def __init__(self, c_puct, num_simulations, evaluate=None, dirichlet_alpha=0.03,
-                 dirichlet_epsilon=0.0, rng=None, leaves_per_step=1):
+                 dirichlet_epsilon=0.0, rng=None, leaves_per_step=1, node_capacity=None):
         self.c_puct = c_puct
+        # the engine's node arena (engine.hip expand_backup_leaf: `if (fc + nc <= p.C)`), not
+        # the reference's: an expansion that would not fit is skipped and counted, its value
+        # still backed up.  None = the reference's unbounded tree.
+        self.node_capacity = node_capacity
+        self.overflows = 0
         self.K = max(1, int(leaves_per_step))
         self.sims = num_simulations
         self.evaluate = evaluate  # (own, opp, player) -> (priors f32[65], value float)
@@ -188,6 +200,9 @@ class SeqMCTS:
             priors = (1 - self.eps) * priors + self.eps * noise
         valid = np.zeros(65, np.uint8)
         acts = self.valid_actions(i)
+        if self.node_capacity is not None and len(self.own) + len(acts) > self.node_capacity:
+            self.overflows += 1  # no children; the caller still backs v up
+            return v
         valid[acts] = 1
         priors = priors * valid
         tot = priors.sum()
