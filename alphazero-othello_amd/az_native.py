@@ -71,6 +71,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
+_U32 = ctypes.c_uint32
 _U64 = ctypes.c_uint64
 _D = ctypes.c_double
 
@@ -157,6 +158,9 @@ SIGNATURES = {
     "oth_records_cpu": [_P, _I32, _P, _P, _P, _I64, _I32, _I32] + [_P] * 12,
     "oth_records_gpu": [_P, _I32, _P, _P, _P, _I64, _I32, _I32] + [_P] * 12 + [_P],
     "az_records_vote_gpu": [_P] * 4 + [_I64] + [_P] * 9,
+    "az_rng_uniform_cpu": [_U64, _U32, _U32, _I64, _U32, _U32, _P],
+    "az_rng_uniform_gpu": [_U64, _U32, _U32, _I64, _U32, _U32, _P, _P],
+    "az_rng_dirichlet_gpu": [_U64, _U32, _U32, _I64, _U32, _D, _P, _P, _P],
 }
 
 
@@ -360,6 +364,41 @@ def search_cpu(own, opp, depth, node_limit=1 << 31):
     check(lib.oth_search_cpu(ptr(own), ptr(opp), own.size, int(depth), int(node_limit),
                              ptr(value), ptr(best), ptr(nodes)), "oth_search_cpu")
     return value, best, nodes
+
+
+# ---- test support: the engine's device random draws as arrays (csrc/rng_probe.hip) --------
+
+def rng_uniform_cpu(seed, stream_id, slot0, n, event, sub):
+    """azr::uniform2 on the host for slots slot0 .. slot0 + n - 1: double [n, 2]."""
+    out = np.empty((int(n), 2), np.float64)
+    check(lib.az_rng_uniform_cpu(int(seed), int(stream_id), int(slot0), int(n), int(event),
+                                 int(sub), ptr(out)), "az_rng_uniform_cpu")
+    return out
+
+
+def rng_uniform_gpu(seed, stream_id, slot0, n, event, sub, device="cuda"):
+    """The same draws from the device: a float64 device tensor [n, 2]."""
+    import torch
+
+    out = torch.empty((int(n), 2), dtype=torch.float64, device=device)
+    with torch.cuda.device(out.device):
+        check(lib.az_rng_uniform_gpu(int(seed), int(stream_id), int(slot0), int(n), int(event),
+                                     int(sub), ptr(out), stream_ptr()), "az_rng_uniform_gpu")
+    return out
+
+
+def rng_dirichlet_gpu(seed, stream_id, slot0, n, event, alpha, device="cuda"):
+    """A root expansion's noise draw per slot: float64 device tensors (gammas [n, 65] raw,
+    noise [n, 65] normalised)."""
+    import torch
+
+    gammas = torch.empty((int(n), 65), dtype=torch.float64, device=device)
+    noise = torch.empty_like(gammas)
+    with torch.cuda.device(gammas.device):
+        check(lib.az_rng_dirichlet_gpu(int(seed), int(stream_id), int(slot0), int(n), int(event),
+                                       float(alpha), ptr(gammas), ptr(noise), stream_ptr()),
+              "az_rng_dirichlet_gpu")
+    return gammas, noise
 
 
 def status_flags(st):

@@ -1024,14 +1024,10 @@ __device__ double expand_backup_leaf(const Params& p, int g, int half, const Lea
         if (lane == 0) p.g.noise_cur[g] = cur + 1;
       } else {
         const uint32_t ev = p.g.rng_event[g];
-        const double ga = azr::gamma_draw(p.alpha, p.seed, (uint32_t)g, ev, (uint32_t)lane, p.stream_id);
-        const double ga64 = azr::gamma_draw(p.alpha, p.seed, (uint32_t)g, ev, 64u, p.stream_id);
-        double s = ga;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
-        s += ga64;
-        n = ga / s;
-        n64 = ga64 / s;
+        const azr::Dirichlet65 dn =
+            azr::dirichlet65(p.alpha, p.seed, (uint32_t)g, ev, (uint32_t)lane, p.stream_id);
+        n = dn.n;
+        n64 = dn.n64;
         if (lane == 0) p.g.rng_event[g] = ev + 1;
       }
       // (1 - eps) * priors is float32 (Python float x float32 array); + eps * noise is float64
@@ -2114,6 +2110,12 @@ int az_engine_create(const az_config* cfg_in, az_engine** out) {
   if (cfg.leaves_per_step <= 0) cfg.leaves_per_step = 1;
   AZ_REQUIRE(cfg.leaves_per_step <= kMaxLeaves, AZ_ERR_ARG,
              "leaves_per_step must be in [1, %d], got %d", kMaxLeaves, cfg.leaves_per_step);
+  // the Philox counter holds 32 bits of stream id, and gamma_draw takes its second pair of
+  // uniforms from stream ^ 0x80000000: ids 2^31 apart would share those draws
+  AZ_REQUIRE(cfg.stream_id < (1ull << 31), AZ_ERR_ARG,
+             "stream_id must be below 2^31, got %llu: the Philox counter holds 32 bits of it "
+             "and the gamma sampler's second stream is stream_id ^ 0x80000000",
+             (unsigned long long)cfg.stream_id);
 
   az_engine* e = new (std::nothrow) az_engine();
   AZ_REQUIRE(e, AZ_ERR_ARG, "out of host memory");

@@ -80,4 +80,26 @@ __device__ inline double gamma_draw(double alpha, uint64_t seed, uint32_t slot, 
   return d;  // practically unreachable (acceptance rate > 95% per trial)
 }
 
+// One Dirichlet(alpha) vector over the 65 actions by a whole wavefront (np.random.dirichlet,
+// MCTS_model.py:340-343): lane a draws the gamma of action a (sub-draw range a), every lane
+// draws the pass's (range 64) redundantly, the sum is an xor butterfly over the lanes plus
+// the pass's.  ga / ga64: the raw gammas, n / n64: the normalised components.
+struct Dirichlet65 {
+  double ga, ga64, n, n64;
+};
+
+__device__ inline Dirichlet65 dirichlet65(double alpha, uint64_t seed, uint32_t slot,
+                                          uint32_t event, uint32_t lane, uint32_t stream) {
+  Dirichlet65 r;
+  r.ga = gamma_draw(alpha, seed, slot, event, lane, stream);
+  r.ga64 = gamma_draw(alpha, seed, slot, event, 64u, stream);
+  double s = r.ga;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s += r.ga64;
+  r.n = r.ga / s;
+  r.n64 = r.ga64 / s;
+  return r;
+}
+
 }  // namespace azr

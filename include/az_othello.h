@@ -268,7 +268,8 @@ typedef struct az_config {
   int32_t inj_noise_slots;       /* AZ_RNG_INJECTED: Dirichlet vectors per slot */
   int32_t inj_uniform_slots;     /* AZ_RNG_INJECTED: uniforms per slot */
   uint64_t seed;                 /* Philox key */
-  uint64_t stream_id;            /* Philox sub-stream (rank) */
+  uint64_t stream_id;            /* Philox sub-stream (rank); below 2^31 (AZ_ERR_ARG otherwise:
+                                    the gamma sampler also draws from stream_id ^ 0x80000000) */
   int32_t leaves_per_step;       /* K in [1, 8] (0 -> 1): leaves per slot per step, the
                                     reference's args['num_threads'] workers with virtual loss
                                     (MCTS_model.py:115-118, :196-197, :372-395) in one fixed
@@ -356,6 +357,27 @@ int az_select_expand(az_engine* eng, float* nn_in, int32_t* leaf_o, const float*
  * [G, inj_uniform_slots] (consumed by the temperature-0 tie break and the action sample,
  * in the reference's np.random call order).  Resets the cursors.  Synchronous. */
 int az_inject(az_engine* eng, const double* noise, const double* uniforms, void* stream);
+
+/* ---- test support, not reference routines: the AZ_RNG_DEVICE draws as arrays
+ * (csrc/rng_probe.hip).  They run the engine's own sampler code (csrc/philox.h) and exist
+ * so the tests can hold it against references of their own.  A draw's Philox4x32-10 counter is
+ * (slot, event, sub, stream_id), its key the seed's low and high words; slots are
+ * slot0 + i mod 2^32.
+ * az_rng_uniform_*: out[2i], out[2i+1] = the two doubles in [0, 1) of slot slot0 + i's draw
+ * at (event, sub): the first 64 and the last 64 output bits, each >> 11, / 2^53.  _cpu: host
+ * pointer, host code; _gpu: device pointer, one thread per slot, n < 2^31.
+ * az_rng_dirichlet_gpu: per slot what a root expansion draws at `event` with
+ * dirichlet_alpha = alpha, one wavefront per slot as in the engine: gammas double [n][65] the
+ * raw Gamma(alpha, 1) draws (action a from sub-draws a*64 + trial), noise double [n][65]
+ * the vector the priors are mixed with.  stream_id >= 2^31 is AZ_ERR_ARG as in
+ * az_engine_create.  Device pointers, asynchronous on `stream`. */
+int az_rng_uniform_cpu(uint64_t seed, uint32_t stream_id, uint32_t slot0, int64_t n,
+                       uint32_t event, uint32_t sub, double* out);
+int az_rng_uniform_gpu(uint64_t seed, uint32_t stream_id, uint32_t slot0, int64_t n,
+                       uint32_t event, uint32_t sub, double* out, void* stream);
+int az_rng_dirichlet_gpu(uint64_t seed, uint32_t stream_id, uint32_t slot0, int64_t n,
+                         uint32_t event, double alpha, double* gammas, double* noise,
+                         void* stream);
 
 /* pi of one slot's root (MCTS_model.py:244-271) at temperature `temp`; u_tie in [0,1)
  * picks among tied maxima at temp < 0.1 (index floor(u_tie * n_ties)).  Optional outputs:
