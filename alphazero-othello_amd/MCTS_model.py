@@ -175,7 +175,9 @@ class _EngineSearch:
         self.engine = Engine(1, self.args["num_simulations"], c_puct=self.args["c_puct"],
                              dirichlet_alpha=self.alpha, dirichlet_epsilon=self.eps,
                              rollout=self.policy is None, injected_rng=True, auto_play=False,
-                             leaves_per_step=self.K)
+                             leaves_per_step=self.K,
+                             leaf_solve_empties=self.args.get("leaf_solve_empties", 0),
+                             leaf_solve_nodes=self.args.get("leaf_solve_nodes"))
         if isinstance(self.policy, torch.nn.Module) and hasattr(self.policy, "evaluate_planes"):
             import copy
 
@@ -192,6 +194,11 @@ class _EngineSearch:
         self._tree = None
 
     def _evaluate(self):
+        self._evaluate_policy()
+        if self.engine.leaf_empties:  # args["leaf_solve_empties"]: exact values for late leaves
+            self.engine.leaf_solve()
+
+    def _evaluate_policy(self):
         import torch
 
         e = self.engine

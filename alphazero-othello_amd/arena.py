@@ -75,7 +75,9 @@ class BatchedArena:
                 self.eng[k] = Engine(n_slots, args["num_simulations"], rollout=net is None,
                                      seed=seed + k, c_puct=args["c_puct"], auto_play=False,
                                      node_capacity=node_capacity, device=device,
-                                     leaves_per_step=self.K)
+                                     leaves_per_step=self.K,
+                                     leaf_solve_empties=args.get("leaf_solve_empties", 0),
+                                     leaf_solve_nodes=args.get("leaf_solve_nodes"))
                 self.eval[k] = _as_evaluator(net, self.eng[k].device)
         self.tie_break = tie_break
         # graphs need every evaluator on device buffers only (rollout or a fused inference
@@ -114,6 +116,8 @@ class BatchedArena:
                 pr, va = ev(e.nn_in[r0:r1])
                 e.priors[r0:r1].copy_(pr)
                 e.values[r0:r1].copy_(va)
+            if e.leaf_empties:  # args["leaf_solve_empties"]: exact values for late leaves
+                e.leaf_solve(e.values[r0:r1], e.nn_in[r0:r1])
             e.expand()
 
     def _run(self, plan, n):

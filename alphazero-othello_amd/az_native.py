@@ -151,6 +151,9 @@ SIGNATURES = {
     "oth_solve_gpu": [_P, _P, _I64, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
     "oth_solve_deep_cpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _P, _P, _P],
     "oth_solve_deep_gpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
+    "az_leaf_solve_cpu": [_P, _P, _I64, _I32, _U64, _P],
+    "az_leaf_solve_gpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
+    "az_leaf_solve_stats_gpu": [_P, _P, _P],
     "oth_eval_cpu": [_P, _P, _I64, _P],
     "oth_eval_gpu": [_P, _P, _I64, _P, _P],
     "oth_search_cpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
@@ -344,6 +347,60 @@ def solve_deep_gpu(own, opp, max_empties=16, alpha=-65, beta=65, node_limit=1 <<
                                          ptr(nodes), ptr(ws), ctypes.byref(need),
                                          stream_ptr(s)), "oth_solve_deep_gpu")
     return score, best, nodes
+
+
+AZ_LEAF_SOLVE_MAX_EMPTIES = 12
+LEAF_SOLVE_STATS = ("solved", "limited", "nodes")
+
+
+def leaf_solve_cpu(nn_in, values, max_empties, node_limit):
+    """az_leaf_solve_cpu on host arrays: `values` (float32 [rows], C-contiguous) is updated
+    in place from the planes nn_in (float32 [rows, 64]); returns this call's counters."""
+    nn_in = np.ascontiguousarray(nn_in, np.float32)
+    assert values.dtype == np.float32 and values.flags["C_CONTIGUOUS"]
+    rows = values.size
+    assert nn_in.size == rows * 64
+    stats = np.zeros(3, np.uint64)
+    check(lib.az_leaf_solve_cpu(ptr(nn_in), ptr(values), rows, int(max_empties),
+                                int(node_limit), ptr(stats)), "az_leaf_solve_cpu")
+    return dict(zip(LEAF_SOLVE_STATS, (int(x) for x in stats)))
+
+
+def leaf_solve_workspace(rows, device):
+    """A zeroed workspace for az_leaf_solve_gpu calls of up to `rows` rows (one owner, one
+    stream)."""
+    import torch
+
+    need = ctypes.c_size_t(0)
+    check(lib.az_leaf_solve_gpu(None, None, int(rows), 1, 1, None, ctypes.byref(need), None),
+          "az_leaf_solve_gpu")
+    return torch.zeros(need.value // 8, dtype=torch.int64, device=device)
+
+
+def leaf_solve_gpu(nn_in, values, max_empties, node_limit, workspace, stream=None):
+    """az_leaf_solve_gpu on device tensors (row slices of larger buffers are fine),
+    asynchronous on `stream` (default: the current stream); `values` is updated in place."""
+    import torch
+
+    rows = values.numel()
+    assert nn_in.dtype == values.dtype == torch.float32
+    assert nn_in.is_contiguous() and values.is_contiguous() and nn_in.numel() == rows * 64
+    have = ctypes.c_size_t(workspace.numel() * workspace.element_size())
+    with torch.cuda.device(values.device):
+        check(lib.az_leaf_solve_gpu(ptr(nn_in), ptr(values), rows, int(max_empties),
+                                    int(node_limit), ptr(workspace), ctypes.byref(have),
+                                    stream_ptr(stream)), "az_leaf_solve_gpu")
+
+
+def leaf_solve_stats_gpu(workspace, stream=None):
+    """The counters accumulated in a workspace (synchronises `stream`)."""
+    import torch
+
+    stats = np.zeros(3, np.uint64)
+    with torch.cuda.device(workspace.device):
+        check(lib.az_leaf_solve_stats_gpu(ptr(workspace), ptr(stats), stream_ptr(stream)),
+              "az_leaf_solve_stats_gpu")
+    return dict(zip(LEAF_SOLVE_STATS, (int(x) for x in stats)))
 
 
 def eval_cpu(own, opp):

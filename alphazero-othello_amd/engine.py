@@ -8,6 +8,7 @@ graphs of 8 steps).  The plain sequence (Engine's host-driven API, the drop-in M
     az_select         leaves of every active game -> canonical planes nn_in [G*K, 64]
                       (K = leaves_per_step: virtual-loss descents per game per step)
     net               the leaf evaluation on nn_in -> priors [G*K, 65], values [G*K]
+    (az_leaf_solve)   args["leaf_solve_empties"] > 0 only: exact values for late leaves
     az_expand_backup  expansion + backup
     az_play           games whose search finished: pi, record, sample, move, TD(lambda)
                       targets on game end, re-root; finished slots restart
@@ -31,6 +32,24 @@ import az_native as nat
 SAMPLE_FIELDS = ("own", "opp", "pi", "z", "player", "slot")
 
 
+# args["leaf_solve_nodes"] when absent: the smallest power of two that left under 1 % of a
+# self-play run's leaves with 1..6 empties unsolved ("Exact leaf values")
+LEAF_SOLVE_NODES = 256
+
+
+def leaf_solve_args(args):
+    """(leaf_solve_empties, leaf_solve_nodes) of an args dict: 0..12 (0 or absent = off) and
+    the node limit of one leaf's search."""
+    e = int(args.get("leaf_solve_empties") or 0)
+    if not 0 <= e <= nat.AZ_LEAF_SOLVE_MAX_EMPTIES:
+        raise ValueError(f"leaf_solve_empties={e} outside 0..{nat.AZ_LEAF_SOLVE_MAX_EMPTIES}")
+    n = args.get("leaf_solve_nodes")
+    n = LEAF_SOLVE_NODES if n is None else int(n)
+    if n < 1:
+        raise ValueError(f"leaf_solve_nodes={n} < 1")
+    return e, n
+
+
 class Engine:
     """RAII owner of one az_engine handle plus its per-step device buffers."""
 
@@ -39,7 +58,8 @@ class Engine:
                  lambd=1.0, rollout=False, injected_rng=False, d4_augment=False,
                  auto_play=True, refill=False, node_capacity=0, max_plies=0,
                  sample_capacity=0, inj_noise_slots=1, inj_uniform_slots=1, seed=0,
-                 stream_id=0, device=None, leaves_per_step=1):
+                 stream_id=0, device=None, leaves_per_step=1, leaf_solve_empties=0,
+                 leaf_solve_nodes=None):
         if not torch.cuda.is_available():
             raise RuntimeError("the self-play engine needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else "cuda")
@@ -71,6 +91,13 @@ class Engine:
         self.param_epoch = 0
         self.K = max(1, int(leaves_per_step))
         self.rollout = rollout
+        # exact leaf values (leaf_solve): off at 0; the workspace exists only when it is on
+        self.leaf_empties, self.leaf_nodes = leaf_solve_args(
+            {"leaf_solve_empties": leaf_solve_empties, "leaf_solve_nodes": leaf_solve_nodes})
+        if self.leaf_empties and rollout:
+            raise ValueError("leaf_solve_empties > 0 needs a net: rollout evaluation ignores "
+                             "`values`")
+        self.leaf_ws = None
         with torch.cuda.device(self.device):
             h = ctypes.c_void_p()
             nat.check(nat.lib.az_engine_create(ctypes.byref(cfg), ctypes.byref(h)),
@@ -86,6 +113,8 @@ class Engine:
             self.leaf = torch.full((R,), -1, dtype=torch.int32, device=d)
             self.priors = torch.zeros(R, 65, dtype=torch.float32, device=d)
             self.values = torch.zeros(R, dtype=torch.float32, device=d)
+            if self.leaf_empties:
+                self.leaf_ws = nat.leaf_solve_workspace(R, d)
 
     def close(self):
         if getattr(self, "h", None):
@@ -117,6 +146,27 @@ class Engine:
 
     def play(self):
         nat.check(nat.lib.az_play(self.h, self._s()), "az_play")
+
+    def leaf_solve(self, values=None, nn_in=None):
+        """Exact leaf values (az_leaf_solve_gpu), enqueued between an evaluation and the
+        expansion that reads it: every row of nn_in (default: all; row slices are fine) with
+        1..leaf_solve_empties empties gets values[row] = the sign of its solved score, unless
+        its search passes leaf_solve_nodes nodes.  The value does not change under the board's
+        symmetries, so D4-augmented rows need nothing extra.  The workspace is this engine's:
+        one stream at a time."""
+        if not self.leaf_empties:
+            raise RuntimeError("leaf solving is off (leaf_solve_empties = 0)")
+        va = self.values if values is None else values
+        x = self.nn_in if nn_in is None else nn_in
+        assert va.numel() <= self.G * self.K
+        nat.leaf_solve_gpu(x, va, self.leaf_empties, self.leaf_nodes, self.leaf_ws)
+
+    def leaf_solve_stats(self):
+        """{"solved", "limited", "nodes"}: rows given an exact value, rows left to the net
+        at the node limit, and the nodes of both, since the engine was made."""
+        if self.leaf_ws is None:
+            return dict.fromkeys(nat.LEAF_SOLVE_STATS, 0)
+        return nat.leaf_solve_stats_gpu(self.leaf_ws)
 
     # deferred moves (include/az_othello.h): step n's move phase inside step n+1's select launch
     def defer_moves(self, on=True):
@@ -319,7 +369,10 @@ class BatchedSelfPlay:
     channels-last, trunk `precision` "fp16x2" (fp32-accurate, default for fp32) / "split3" / "fp32" /
     "fp16" = config #5).  `args` uses the reference's keys
     (train.py:399-423): c_puct, num_simulations, dirichlet_alpha, dirichlet_epsilon,
-    mcts_temperature, num_exploratory_moves, lambda.
+    mcts_temperature, num_exploratory_moves, lambda; and two of this engine's own:
+    leaf_solve_empties (0..12, default 0 = off: leaves with that many empties at most are
+    solved to win / draw / loss before their value is backed up, Engine.leaf_solve) and
+    leaf_solve_nodes (the node limit of one such search).
     """
 
     def __init__(self, net, args, n_games, seed=0, stream_id=0, d4_augment=False,
@@ -340,7 +393,9 @@ class BatchedSelfPlay:
             auto_play=True, refill=True, node_capacity=node_capacity,
             sample_capacity=sample_capacity, seed=seed, stream_id=stream_id, device=device,
             leaves_per_step=leaves_per_step, injected_rng=injected_rng,
-            inj_noise_slots=inj_noise_slots, inj_uniform_slots=inj_uniform_slots)
+            inj_noise_slots=inj_noise_slots, inj_uniform_slots=inj_uniform_slots,
+            leaf_solve_empties=args.get("leaf_solve_empties", 0),
+            leaf_solve_nodes=args.get("leaf_solve_nodes"))
         self.device = self.engine.device
         if net is None:
             self.net = None
@@ -397,6 +452,8 @@ class BatchedSelfPlay:
                 pr, va = self.net.evaluate_planes(e.nn_in)
                 e.priors.copy_(pr)
                 e.values.copy_(va)
+            if e.leaf_empties:  # exact values for late leaves, before any expansion reads them
+                e.leaf_solve()
         if self.fuse_expand:
             pass  # expanded by the next step's launch (or step()'s flush)
         elif self.defer_moves:

@@ -433,6 +433,8 @@ def _local_rows(policy, args, num_games, n_slots, seed, stream_id, d4_augment, d
     from engine import BatchedSelfPlay, PipelinedSelfPlay
 
     n_slots = n_slots or min(num_games, 4096)
+    # args goes to the engine whole: args["leaf_solve_empties"] / ["leaf_solve_nodes"] (exact
+    # values for late leaves, engine.Engine.leaf_solve) take effect on every batch path
     kw = dict(seed=seed, stream_id=stream_id, d4_augment=d4_augment, dtype=dtype,
               sample_capacity=num_games * 130,
               leaves_per_step=min(8, max(1, int(args.get("num_threads", 4)))))

@@ -178,6 +178,32 @@ int oth_solve_deep_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int3
                        int8_t* score_o, uint8_t* best_o, uint64_t* nodes_o, void* workspace,
                        size_t* workspace_bytes, void* stream);
 
+/* ---------------- exact values for late leaves of the search --------------------------
+ * A pass between a leaf evaluation and the expansion that reads it (csrc/leaf_solve.hip).
+ * Row r of nn_in is 64 floats in {-1, 0, +1}, the canonical planes of a leaf: own (the side
+ * to move) = the squares with x > 0.5, opp = the squares with x < -0.5.  A row with
+ * e = 64 - popcount(own | opp) in 1..max_empties is searched by the windowed solver above,
+ * unsplit, in (-1, 1), with node_limit nodes; if the search finishes, values[r] becomes
+ * -1.0f, 0.0f or +1.0f, the sign of its score.  Every other row keeps its value bit for bit:
+ * an all-zero row (no leaf), e = 0, e > max_empties, and a row whose search passed
+ * node_limit (the evaluator's value stays).  max_empties outside
+ * 1..AZ_LEAF_SOLVE_MAX_EMPTIES or node_limit = 0 is AZ_ERR_ARG.
+ * stats3 = {rows solved, rows left at the node limit, nodes of both}. */
+#define AZ_LEAF_SOLVE_MAX_EMPTIES 12
+/* host mirror: host pointers; stats3 (may be NULL) receives this call's counts */
+int az_leaf_solve_cpu(const float* nn_in, float* values, int64_t rows, int32_t max_empties,
+                      uint64_t node_limit, uint64_t* stats3);
+/* device pointers, asynchronous on `stream`, rows < 2^31: a counter reset and two kernels in
+ * a linear chain, without host synchronisation or allocation (it captures into a HIP graph).
+ * Call with workspace = NULL to get *workspace_bytes (a function of rows), then with that
+ * much 8-byte aligned device memory, zeroed once by its owner.  The counters accumulate in
+ * the workspace across calls until it is zeroed again.  A workspace belongs to one caller on
+ * one stream: two streams running at once must not share one. */
+int az_leaf_solve_gpu(const float* nn_in, float* values, int64_t rows, int32_t max_empties,
+                      uint64_t node_limit, void* workspace, size_t* workspace_bytes, void* stream);
+/* the counters of a workspace, read after the work queued on `stream` (synchronous) */
+int az_leaf_solve_stats_gpu(const void* workspace, uint64_t* stats3, void* stream);
+
 /* ---------------- depth-limited alpha-beta with a heuristic evaluation ----------------
  * Integer-only and identical on host and device (csrc/search.h).  own = side to move.
  *   h(own, opp) = sum_sq W[sq] * ([sq in own] - [sq in opp])
