@@ -137,11 +137,26 @@
 #ifndef AZ_W4_TRUNK_BOARDS
 #define AZ_W4_TRUNK_BOARDS 2
 #endif
+// single-issue fp32 beside the MFMAs (bits): the two-wide adds, subtractions, products and
+// FMAs of 1 = the resident trunk's input transform (combine_kx, col_comb), 2 = the fold, 4 =
+// the epilogues' output pairs as two one-lane-wide instructions each instead of one
+// v_pk_*_f32; the same IEEE operations element by element, outputs bit-identical.  Bit 1 is
+// pinned by asm forms; bits 2 and 4 are plain expressions that -O3 pairs again unless the file
+// is built with -fno-slp-vectorize (scripts/build_variants.py NAME "-DAZ_W4_F32S=7
+// -fno-slp-vectorize").  B = 1,024 trunk + heads launch, builds interleaved on one box
+// (profiles/trunk_f32_issue_ab.json): bit 1 343.8 -> 338.6 us (the parent's round-to-round
+// range 1.2 us), configs[2] 129.6-130.3 -> 131.7-132.2 games/s; bit 2 alone 1.4 us slower, bit
+// 4 alone 1.9 us faster (inside the noise margin), all three 4.4 us faster -- less than bit 1
+// alone, so only bit 1 ships.  The per-layer kernels keep the packed transform (their code is
+// the same as before, instruction for instruction)
+#ifndef AZ_W4_F32S
+#define AZ_W4_F32S 1
+#endif
 // the epilogue's output pairs (2tx, 2tx + 1) as packed f32x2 (scale + bias in one v_pk_fma_f32,
 // the staged residual in one packed add): 411.0-411.5 -> 409.0-410.3 us per B = 1,024 trunk
 // + heads launch, same box (profiles/r05_conv_micro_ab.json); 0 = one element at a time
 #ifndef AZ_W4_EPI_PK
-#define AZ_W4_EPI_PK 1
+#define AZ_W4_EPI_PK !(AZ_W4_F32S & 4)
 #endif
 // the persistent trunk's layer hand-off: a layer's epilogue also writes its output's first two
 // 16-channel slices (channels 0-31, held by the column-block-0 wave) into the input slots and
@@ -497,6 +512,72 @@ __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
 #endif
 }
 
+// a - b on an f32x2 as ONE v_pk_add_f32 with b negated: the compiler splits a two-wide
+// fsub into two v_sub_f32 (and folds an fma by -1 back into that fsub); same IEEE
+// differences element by element
+__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
+#if AZ_W4_PK
+  f32x2 r;
+  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+#else
+  return a - b;
+#endif
+}
+
+// one single-issue fp32 instruction, as asm so that -O3 cannot pair two of them into a
+// v_pk_*_f32 again (AZ_W4_F32S bit 1: the transform's operands come from LDS reads and plain
+// VALU, never straight from an MFMA)
+__device__ __forceinline__ float s_add(float a, float b) {
+  float r;
+  asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float s_sub(float a, float b) {
+  float r;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float s_mul(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float s_fma(float a, float b, float c) {
+  float r;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+// the transform's (bit 1) and the fold's (bit 2) two-wide operations: packed, or with the bit
+// set in AZ_W4_F32S one single-issue instruction per element (bit 1 pinned by the asm forms
+// above; bit 2 as plain expressions, which stay single only under -fno-slp-vectorize)
+template <int BIT>
+__device__ __forceinline__ f32x2 f2_add(f32x2 a, f32x2 b) {
+  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_add(a.x, b.x), s_add(a.y, b.y)};
+  if constexpr ((AZ_W4_F32S & BIT) != 0) return f32x2{a.x + b.x, a.y + b.y};
+  return pk_add(a, b);
+}
+template <int BIT>
+__device__ __forceinline__ f32x2 f2_sub(f32x2 a, f32x2 b) {
+  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_sub(a.x, b.x), s_sub(a.y, b.y)};
+  if constexpr ((AZ_W4_F32S & BIT) != 0) return f32x2{a.x - b.x, a.y - b.y};
+  return pk_sub(a, b);
+}
+template <int BIT>
+__device__ __forceinline__ f32x2 f2_mul(f32x2 a, float b) {
+  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_mul(a.x, b), s_mul(a.y, b)};
+  if constexpr ((AZ_W4_F32S & BIT) != 0) return f32x2{a.x * b, a.y * b};
+  return pk_mul(a, f32x2{b, b});
+}
+// fma(a, b, c), b one scalar
+template <int BIT>
+__device__ __forceinline__ f32x2 f2_fma(f32x2 a, float b, f32x2 c) {
+  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_fma(a.x, b, c.x), s_fma(a.y, b, c.y)};
+  if constexpr ((AZ_W4_F32S & BIT) != 0)
+    return f32x2{__builtin_fmaf(a.x, b, c.x), __builtin_fmaf(a.y, b, c.y)};
+  return pk_fma(a, f32x2{b, b}, c);
+}
+
 template <int KK>
 __device__ __forceinline__ void combine_k(f32x2 (&rk)[4], const f32x2 (&d)[8], float vsc) {
   const f32x2 fa = {grp_sa(KK) * vsc, grp_sa(KK) * vsc}, fb = {grp_sb(KK) * vsc, grp_sb(KK) * vsc};
@@ -536,6 +617,16 @@ __device__ __forceinline__ void read_rows_x(f32x2 (&d)[8], const char* lds, cons
   }
 }
 
+// the column edge masks folded into the per-column coefficients instead of multiplied into the
+// combined rows.  Not only two operations fewer per chunk: an off-board window entry is whatever
+// finite word lies there (X, or a V buffer's fp16 pairs read as fp32: up to 2^121 for the fp16
+// Inf pairs of an absent board's overflowed rows), and coefficient x word could overflow to Inf
+// BEFORE the mask's x 0 -- NaN in the top-left window of a workgroup's first board, e.g. B = 5
+// boards with the last one's input range >= 64 alone in its workgroup (tests/
+// test_trunk_f32_issue_gpu.py).  0 = the masks applied after the combination (A/B builds)
+#ifndef AZ_W4_CMASK
+#define AZ_W4_CMASK 1
+#endif
 // combine_k with the board-edge masks m = {top row valid, bottom row valid, left column valid,
 // right column valid} (0 / 1): a masked term is finite x 0, so the sums are the zero-padded
 // slot's (up to the sign of an exact zero)
@@ -545,33 +636,37 @@ __device__ __forceinline__ void combine_kx(f32x2 (&rk)[4], const f32x2 (&d)[8], 
   float fa_s = grp_sa(KK) * vsc, fb_s = grp_sb(KK) * vsc;
   if constexpr (KK == 0) fa_s *= m[0];  // window row 2ty - 1
   if constexpr (KK == 3) fb_s *= m[1];  // window row 2ty + 2
+#if AZ_W4_CMASK
+  // the column masks in the coefficients of columns 2tx - 1 and 2tx + 2: a masked entry is
+  // coefficient 0 x a finite word = 0 whatever the word's size
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const float fa_b = b == 0 ? fa_s * m[2] : b == 3 ? fa_s * m[3] : fa_s;
+    const float fb_b = b == 0 ? fb_s * m[2] : b == 3 ? fb_s * m[3] : fb_s;
+    rk[b] = f2_fma<1>(d[4 + b], fb_b, f2_mul<1>(d[b], fa_b));
+  }
+#elif AZ_W4_F32S & 1
+#pragma unroll
+  for (int b = 0; b < 4; ++b) rk[b] = f2_fma<1>(d[4 + b], fb_s, f2_mul<1>(d[b], fa_s));
+  rk[0] = f2_mul<1>(rk[0], m[2]);  // window column 2tx - 1
+  rk[3] = f2_mul<1>(rk[3], m[3]);  // window column 2tx + 2
+#else
   const f32x2 fa = {fa_s, fa_s}, fb = {fb_s, fb_s};
 #pragma unroll
   for (int b = 0; b < 4; ++b) rk[b] = __builtin_elementwise_fma(fb, d[4 + b], fa * d[b]);
   rk[0] = rk[0] * f32x2{m[2], m[2]};  // window column 2tx - 1
   rk[3] = rk[3] * f32x2{m[3], m[3]};  // window column 2tx + 2
-}
-
-// a - b on an f32x2 as ONE v_pk_add_f32 with b negated: the compiler splits a two-wide
-// fsub into two v_sub_f32 (and folds an fma by -1 back into that fsub); same IEEE
-// differences element by element
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-#if AZ_W4_PK
-  f32x2 r;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-#else
-  return a - b;
 #endif
 }
 
 // V at point (k, l) = (row k of B^T d) B: column combination l
-template <int l>
+// BIT = 1: single-issue with AZ_W4_F32S bit 1 (the resident trunk's chunks); 0 = packed
+template <int l, int BIT = 0>
 __device__ __forceinline__ f32x2 col_comb(const f32x2 (&rk)[4]) {
-  if constexpr (l == 0) return pk_sub(rk[0], rk[2]);
-  if constexpr (l == 1) return pk_add(rk[1], rk[2]);
-  if constexpr (l == 2) return pk_sub(rk[2], rk[1]);
-  return pk_sub(rk[1], rk[3]);
+  if constexpr (l == 0) return f2_sub<BIT>(rk[0], rk[2]);
+  if constexpr (l == 1) return f2_add<BIT>(rk[1], rk[2]);
+  if constexpr (l == 2) return f2_sub<BIT>(rk[2], rk[1]);
+  return f2_sub<BIT>(rk[1], rk[3]);
 }
 
 // split two transformed values into PLANES 16-bit words and store them in their slabs
@@ -609,9 +704,9 @@ __device__ __forceinline__ void put(char* slab, f32x2 v, float vsc) {
   }
 }
 
-template <class G, int l>
+template <class G, int l, int BIT = 0>
 __device__ __forceinline__ void put_point(char* buf, const f32x2 (&rk)[4], int soff, float vsc) {
-  put<G>(buf + l * G::PLANES * G::SLAB + soff, col_comb<l>(rk), vsc);
+  put<G>(buf + l * G::PLANES * G::SLAB + soff, col_comb<l, BIT>(rk), vsc);
 }
 
 // group K's M (acc[l][t]) into the output accumulators Y[i][j][t]; K is a compile-time
@@ -625,33 +720,33 @@ __device__ __forceinline__ void fold(f32x16 (&acc)[4][G::NRT], f32x16 (&Y)[2][2]
     v[e] = x.x;
     v[e + 1] = x.y;
   };
-  auto sub = [](f32x2 a, f32x2 b) { return pk_sub(a, b); };
+  auto sub = [](f32x2 a, f32x2 b) { return f2_sub<2>(a, b); };
 #pragma unroll
   for (int t = 0; t < G::NRT; ++t)
 #pragma unroll
     for (int e = 0; e < 16; e += 2) {
       const f32x2 m0 = get(acc[0][t], e), m1 = get(acc[1][t], e), m2 = get(acc[2][t], e),
                   m3 = get(acc[3][t], e);
-      const f32x2 t0 = pk_add(pk_add(m0, m1), m2), t1 = sub(sub(m1, m2), m3);
+      const f32x2 t0 = f2_add<2>(f2_add<2>(m0, m1), m2), t1 = sub(sub(m1, m2), m3);
       if constexpr (K == 0 && G::NG == 4) {
         set(Y[0][0][t], e, t0);
         set(Y[0][1][t], e, t1);
       } else if constexpr (K == 0) {  // NG = 1: Y starts at zero (rows of other workgroups)
-        set(Y[0][0][t], e, pk_add(get(Y[0][0][t], e), t0));
-        set(Y[0][1][t], e, pk_add(get(Y[0][1][t], e), t1));
+        set(Y[0][0][t], e, f2_add<2>(get(Y[0][0][t], e), t0));
+        set(Y[0][1][t], e, f2_add<2>(get(Y[0][1][t], e), t1));
       } else if constexpr (K == 1) {
-        set(Y[0][0][t], e, pk_add(get(Y[0][0][t], e), t0));
-        set(Y[0][1][t], e, pk_add(get(Y[0][1][t], e), t1));
+        set(Y[0][0][t], e, f2_add<2>(get(Y[0][0][t], e), t0));
+        set(Y[0][1][t], e, f2_add<2>(get(Y[0][1][t], e), t1));
         if constexpr (G::NG == 4) {
           set(Y[1][0][t], e, t0);
           set(Y[1][1][t], e, t1);
         } else {
-          set(Y[1][0][t], e, pk_add(get(Y[1][0][t], e), t0));
-          set(Y[1][1][t], e, pk_add(get(Y[1][1][t], e), t1));
+          set(Y[1][0][t], e, f2_add<2>(get(Y[1][0][t], e), t0));
+          set(Y[1][1][t], e, f2_add<2>(get(Y[1][1][t], e), t1));
         }
       } else if constexpr (K == 2) {
-        set(Y[0][0][t], e, pk_add(get(Y[0][0][t], e), t0));
-        set(Y[0][1][t], e, pk_add(get(Y[0][1][t], e), t1));
+        set(Y[0][0][t], e, f2_add<2>(get(Y[0][0][t], e), t0));
+        set(Y[0][1][t], e, f2_add<2>(get(Y[0][1][t], e), t1));
         set(Y[1][0][t], e, sub(get(Y[1][0][t], e), t0));
         set(Y[1][1][t], e, sub(get(Y[1][1][t], e), t1));
       } else {
@@ -843,10 +938,10 @@ __device__ __forceinline__ void run_chunk(St<G>& S, int v) {
 #pragma unroll
     for (int u = 0; u < G::TPT && !(AZ_W4_EXP & 2) && !NO_NEXT; ++u) {
       const float vs = CT ? 1.0f : S.vsc[u];  // CT: the scale is in rk already
-      if (l == 0) put_point<G, 0>(nxt, S.rk[u], S.soff[u], vs);
-      if (l == 1) put_point<G, 1>(nxt, S.rk[u], S.soff[u], vs);
-      if (l == 2) put_point<G, 2>(nxt, S.rk[u], S.soff[u], vs);
-      if (l == 3) put_point<G, 3>(nxt, S.rk[u], S.soff[u], vs);
+      if (l == 0) put_point<G, 0, RSD>(nxt, S.rk[u], S.soff[u], vs);
+      if (l == 1) put_point<G, 1, RSD>(nxt, S.rk[u], S.soff[u], vs);
+      if (l == 2) put_point<G, 2, RSD>(nxt, S.rk[u], S.soff[u], vs);
+      if (l == 3) put_point<G, 3, RSD>(nxt, S.rk[u], S.soff[u], vs);
     }
     if (l < 3) {
 #pragma unroll
