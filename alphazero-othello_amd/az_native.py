@@ -151,6 +151,7 @@ SIGNATURES = {
     "oth_solve_gpu": [_P, _P, _I64, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
     "oth_solve_deep_cpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _P, _P, _P],
     "oth_solve_deep_gpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
+    "oth_solve_moves_cpu": [_P, _P, _I64, _I32, _I32, _U64, _P, _P, _P],
     "az_leaf_solve_cpu": [_P, _P, _I64, _I32, _U64, _P],
     "az_leaf_solve_gpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
     "az_leaf_solve_stats_gpu": [_P, _P, _P],
@@ -347,6 +348,24 @@ def solve_deep_gpu(own, opp, max_empties=16, alpha=-65, beta=65, node_limit=1 <<
                                          ptr(nodes), ptr(ws), ctypes.byref(need),
                                          stream_ptr(s)), "oth_solve_deep_gpu")
     return score, best, nodes
+
+
+AZ_MOVES_NONE = -128
+AZ_MOVES_SCORES, AZ_MOVES_WLD, AZ_MOVES_OPTIMAL = 0, 1, 2
+
+
+def solve_moves_cpu(own, opp, max_empties=12, mode=AZ_MOVES_SCORES, node_limit=1 << 31):
+    """The exact value of every move on the host: (values int8 [n, 65] with AZ_MOVES_NONE
+    where the action is not available, score int8, nodes uint64) per root; see
+    include/az_othello.h for the three modes."""
+    own, opp = _u64(own).reshape(-1), _u64(opp).reshape(-1)
+    values = np.empty((own.size, 65), np.int8)
+    score = np.empty(own.size, np.int8)
+    nodes = np.empty(own.size, np.uint64)
+    check(lib.oth_solve_moves_cpu(ptr(own), ptr(opp), own.size, int(max_empties), int(mode),
+                                  int(node_limit), ptr(values), ptr(score), ptr(nodes)),
+          "oth_solve_moves_cpu")
+    return values, score, nodes
 
 
 AZ_LEAF_SOLVE_MAX_EMPTIES = 12

@@ -14,6 +14,13 @@ host (oth_solve_cpu over a thread pool; ctypes releases the GIL).  On top of it:
 gives the exact win / draw / loss for a fraction of the nodes) and ordered moves, up to 20
 empties; `relabel_rows(wld=True)` and `move_report` beyond 14 empties go through it.
 
+`solve_moves` gives the exact value of every move of a position in one call
+(csrc/solve_moves.hip on the host, composed from the board and solve_deep kernels on the
+device): the whole 65-column table ("scores"), its win / draw / loss signs
+("wld"), or the set of score-optimal moves for fewer nodes ("optimal").  `exact_policy` turns
+a table into a policy target, `relabel_rows(policy=True)` writes it next to the exact z, and
+`policy_report` measures how much of a searched pi lies on optimal moves.
+
 score = final own - opp disc difference from the side to move's view (the reference's plain
 count, envs/othello.py:214-220), best = the lowest optimal action (64 = pass).
 """
@@ -223,25 +230,202 @@ def solve_deep(own, opp, max_empties=16, window=None, device=None, node_limit=1 
     return s, b, nd
 
 
+MOVES_MODES = {"scores": nat.AZ_MOVES_SCORES, "wld": nat.AZ_MOVES_WLD,
+               "optimal": nat.AZ_MOVES_OPTIMAL}
+
+
+def _solve_moves_cpu(own, opp, max_empties, mode, node_limit):
+    """oth_solve_moves_cpu over the same thread pool as _solve_cpu."""
+    n = own.size
+    values = np.empty((n, 65), np.int8)
+    score, nodes = np.empty(n, np.int8), np.empty(n, np.uint64)
+
+    def run(ab):
+        a, b = ab
+        return nat.lib.oth_solve_moves_cpu(nat.ptr(own[a:b]), nat.ptr(opp[a:b]), b - a,
+                                           int(max_empties), int(mode), int(node_limit),
+                                           nat.ptr(values[a:b]), nat.ptr(score[a:b]),
+                                           nat.ptr(nodes[a:b]))
+
+    threads = min(MAX_THREADS, n)
+    if threads <= 1 or not 0 <= max_empties <= nat.AZ_SOLVE_DEEP_MAX_EMPTIES:
+        # one call: the library validates the arguments (and accepts n = 0)
+        nat.check(run((0, n)), "oth_solve_moves_cpu")
+        return values, score, nodes
+    size = max(1, min(256, n // (threads * 8) or 1))  # interleaved, as in _solve_cpu
+    with ThreadPoolExecutor(threads) as ex:
+        rcs = list(ex.map(run, [(a, min(n, a + size)) for a in range(0, n, size)]))
+    for rc in rcs:
+        nat.check(rc, "oth_solve_moves_cpu")
+    return values, score, nodes
+
+
+_SQ = {}
+
+
+def _squares(dev):
+    if dev not in _SQ:
+        _SQ[dev] = torch.arange(64, dtype=torch.int64, device=dev)
+    return _SQ[dev]
+
+
+def _legal_gpu(o_t, p_t):
+    lg = torch.empty_like(o_t)
+    nat.check(nat.lib.oth_legal_gpu(nat.ptr(o_t), nat.ptr(p_t), nat.ptr(lg), o_t.numel(),
+                                    nat.stream_ptr()), "oth_legal_gpu")
+    return lg
+
+
+def solve_moves_gpu_tensors(own, opp, max_empties, mode, node_limit):
+    """oth_solve_moves_cpu's table on int64 device tensors, composed on the current stream from
+    the device entry points there are: oth_legal_gpu -> the available actions expanded in
+    torch -> oth_step_gpu -> oth_solve_deep_gpu, unsplit, on the children (and on the roots
+    first in "optimal" mode, then one children call per distinct root score: the solver takes
+    one window per call) -> scatter.  The searches are the host's, so values (int8 [n, 65]),
+    score (int8) and nodes (int64 bits) are the host's bit for bit.  The expansion reads sizes
+    back to the host, so a call does not capture into a HIP graph."""
+    # the library validates max_empties and mode
+    nat.check(nat.lib.oth_solve_moves_cpu(None, None, 0, int(max_empties), int(mode),
+                                          int(node_limit), None, None, None),
+              "oth_solve_moves_cpu")
+    dev, n = own.device, own.numel()
+    with torch.cuda.device(dev):
+        sq = _squares(dev)
+        count = lambda x: ((x[:, None] >> sq) & 1).sum(dim=1)
+        skip = ((own & opp) != 0) | (64 - count(own | opp) > int(max_empties))
+        lg = torch.where(skip, torch.zeros_like(own), _legal_gpu(own, opp))
+        passer = ~skip & (lg == 0) & (_legal_gpu(opp, own) != 0)
+        par, act = torch.nonzero((lg[:, None] >> sq) & 1, as_tuple=True)
+        pp = torch.nonzero(passer, as_tuple=True)[0]
+        par, act = torch.cat([par, pp]), torch.cat([act, torch.full_like(pp, 64)])
+        k = par.numel()
+        co, cp, cl = (torch.empty(k, dtype=torch.int64, device=dev) for _ in range(3))
+        st = torch.empty(k, dtype=torch.int16, device=dev)
+        ro, rp, act8 = own[par].contiguous(), opp[par].contiguous(), act.to(torch.uint8)
+        nat.check(nat.lib.oth_step_gpu(nat.ptr(ro), nat.ptr(rp), nat.ptr(act8),
+                                       nat.ptr(co), nat.ptr(cp), nat.ptr(cl), nat.ptr(st), k,
+                                       nat.stream_ptr()), "oth_step_gpu")
+        has = torch.zeros(n, dtype=torch.bool, device=dev)
+        has[par] = True
+        # settled roots: skipped (no node), or the game is over (one node, the final difference)
+        score = torch.where(skip, torch.full_like(own, nat.AZ_SOLVE_SKIPPED),
+                            count(own) - count(opp)).to(torch.int8)
+        nodes = (~skip).to(torch.int64)
+        aborted = torch.zeros(n, dtype=torch.bool, device=dev)
+        deep = lambda o, p, a, b: nat.solve_deep_gpu(o, p, nat.AZ_SOLVE_DEEP_MAX_EMPTIES, a, b,
+                                                     node_limit, 0)
+        cs = torch.full((k,), nat.AZ_SOLVE_ABORTED, dtype=torch.int8, device=dev)
+        cn = torch.zeros(k, dtype=torch.int64, device=dev)
+        if mode == nat.AZ_MOVES_OPTIMAL:
+            roots = torch.nonzero(has, as_tuple=True)[0]
+            rs, _, rn = deep(own[roots].contiguous(), opp[roots].contiguous(), -65, 65)
+            score[roots] = rs
+            nodes[roots] += rn
+            aborted[roots] = rs == nat.AZ_SOLVE_ABORTED
+            cw = score[par].to(torch.int64)
+            live = ~aborted[par]  # the children of an aborted root are not searched
+            for s in torch.unique(cw[live]).tolist():
+                g = torch.nonzero(live & (cw == s), as_tuple=True)[0]
+                cs[g], _, cn[g] = deep(co[g].contiguous(), cp[g].contiguous(), -s - 1, -s + 1)
+            searched = live
+        else:
+            w = 1 if mode == nat.AZ_MOVES_WLD else 65
+            cs, _, cn = deep(co, cp, -w, w)
+            searched = torch.ones(k, dtype=torch.bool, device=dev)
+        nodes.index_add_(0, par, cn)
+        aborted[par[searched & (cs == nat.AZ_SOLVE_ABORTED)]] = True
+        values = torch.full((n, 65), nat.AZ_MOVES_NONE, dtype=torch.int8, device=dev)
+        values[par, act] = -(torch.sign(cs) if mode == nat.AZ_MOVES_WLD else cs)
+        if mode != nat.AZ_MOVES_OPTIMAL:
+            score = torch.where(has, values.max(dim=1).values, score)
+        values[aborted] = nat.AZ_MOVES_NONE
+        score[aborted] = nat.AZ_SOLVE_ABORTED
+    return values, score, nodes
+
+
+def solve_moves(own, opp, max_empties=12, mode="scores", device=None, node_limit=1 << 31):
+    """The exact value of every move of every position with at most `max_empties` <= 20
+    empties, in one call: returns (values int8 [n, 65], score, nodes) with `solve_deep`'s
+    array / tensor conventions, device choice, host thread pool and skipped / aborted codes.
+    values[i, a] is AZ_MOVES_NONE (-128) where action a is not available at root i (64 = the
+    pass, available only when the side to move has no placement and the opponent has one).
+
+    mode "scores": values = the exact disc difference each move leads to, score = their
+    maximum.  "wld": values in {-1, 0, 1}, the win / draw / loss each move leads to.
+    "optimal": score = the root's exact score, values == score exactly on the score-optimal
+    moves and a bound below it elsewhere (see include/az_othello.h).  A terminal, skipped or
+    aborted root has an all-NONE row."""
+    if mode not in MOVES_MODES:
+        raise ValueError(f"mode={mode!r}: 'scores', 'wld' or 'optimal'")
+    m = MOVES_MODES[mode]
+    want_torch = isinstance(own, torch.Tensor)
+    dev = _pick_device(device, own, opp)
+    if dev.type == "cuda":
+        v, s, nd = solve_moves_gpu_tensors(_as_i64_tensor(own, dev), _as_i64_tensor(opp, dev),
+                                           max_empties, m, node_limit)
+        if want_torch:
+            return v, s, nd
+        return v.cpu().numpy(), s.cpu().numpy(), nd.cpu().numpy().view(np.uint64)
+    v, s, nd = _solve_moves_cpu(_as_u64_numpy(own), _as_u64_numpy(opp), max_empties, m,
+                                node_limit)
+    if want_torch:
+        return (torch.from_numpy(v).to(own.device), torch.from_numpy(s).to(own.device),
+                torch.from_numpy(nd.view(np.int64)).to(own.device))
+    return v, s, nd
+
+
+def exact_policy(values):
+    """Policy target of a `solve_moves` table (numpy or torch, [n, 65]): float32 [n, 65], each
+    row uniform over the available actions whose value equals the row's maximum; a row
+    without an available action is all zeros."""
+    if isinstance(values, torch.Tensor):
+        return torch.from_numpy(exact_policy(values.detach().cpu().numpy())).to(values.device)
+    v = np.asarray(values).reshape(-1, 65).astype(np.int64)
+    top = v.max(axis=1, keepdims=True)
+    hit = (v == top) & (v != nat.AZ_MOVES_NONE)
+    count = hit.sum(axis=1, keepdims=True)
+    return (hit / np.maximum(count, 1)).astype(np.float32)
+
+
 def _check_solved(score, what):
     if (score == nat.AZ_SOLVE_ABORTED).any():
         raise RuntimeError(f"{what}: {int((score == nat.AZ_SOLVE_ABORTED).sum())} searches "
                            "exceeded the node limit")
 
 
-def relabel_rows(rows, max_empties, device=None, wld=False):
+def relabel_rows(rows, max_empties, device=None, wld=False, policy=False):
     """Exact value targets: in engine sample rows (dict of own / opp / pi / z / player, z
     already from the side to move's view: canonical rows) replace z by float(sign(score)) for
     every row whose position has 1..max_empties empties; other rows and fields are untouched.
     Returns (rows, mask) with mask the boolean array of relabelled rows; `rows` is a new
     dict sharing every array but z.  wld=True takes the sign from solve_deep's (-1, 1)
     window instead of the exact disc count: the same labels for fewer nodes, and max_empties
-    up to 20."""
+    up to 20.
+
+    policy=True: one `solve_moves` call gives both targets of the masked rows; max_empties up
+    to 20 in both settings.  z is what policy=False gives; pi becomes a new array of the
+    input's shape and dtype whose masked rows hold `exact_policy`: uniform over the
+    score-optimal moves (mode "optimal"), or with wld=True over every move that keeps the best
+    reachable win / draw / loss (mode "wld").  A masked row without an available action (the
+    game is over) keeps its pi."""
     own, opp = _as_u64_numpy(rows["own"]), _as_u64_numpy(rows["opp"])
     e = empties(own, opp)
     mask = (e >= 1) & (e <= int(max_empties)) & ((own & opp) == 0)
     out = dict(rows)
     z = np.array(np.asarray(rows["z"]), dtype=np.float64, copy=True)
+    if policy:
+        src = np.asarray(rows["pi"])
+        pi = np.array(src, copy=True)
+        if mask.any():
+            values, score, _ = solve_moves(own[mask], opp[mask], max_empties,
+                                           mode="wld" if wld else "optimal", device=device)
+            _check_solved(score, "relabel_rows")
+            z[mask] = np.sign(score.astype(np.int64)).astype(np.float64)
+            has = (values != nat.AZ_MOVES_NONE).any(axis=1)
+            flat = pi.reshape(-1, 65)
+            flat[np.flatnonzero(mask)[has]] = exact_policy(values[has]).astype(src.dtype)
+        out["z"], out["pi"] = z, pi
+        return out, mask
     if mask.any():
         if wld:
             score, _, _ = solve_deep(own[mask], opp[mask], max_empties, window="wld",
@@ -288,3 +472,34 @@ def move_report(rows, max_empties, device=None):
     root, value = score[:n], -score[n:]
     by = {int(k): _stats(root[e == k], value[e == k]) for k in range(1, int(max_empties) + 1)}
     return {"by_empties": by, "total": _stats(root, value)}
+
+
+def _mass(opt, wld):
+    if len(opt) == 0:
+        return {"n": 0, "optimal_mass": None, "wld_kept_mass": None}
+    return {"n": int(len(opt)), "optimal_mass": float(opt.mean()),
+            "wld_kept_mass": float(wld.mean())}
+
+
+def policy_report(rows, max_empties, device=None):
+    """How much of each row's pi lies on good moves, for every row with 1..max_empties empties
+    and at least one available action (pi as given, not renormalised)?  Every move's exact
+    value comes from one `solve_moves` call in "scores" mode.  Returns {"by_empties": {e:
+    stats}, "total": stats} with stats = n, optimal_mass (mean mass of pi on the
+    score-optimal moves) and wld_kept_mass (mean mass on the moves whose win / draw / loss is
+    the position's own)."""
+    own, opp = _as_u64_numpy(rows["own"]), _as_u64_numpy(rows["opp"])
+    e = empties(own, opp)
+    mask = (e >= 1) & (e <= int(max_empties)) & ((own & opp) == 0)
+    own, opp, e = own[mask], opp[mask], e[mask]
+    pi = np.asarray(rows["pi"], np.float64).reshape(-1, 65)[mask]
+    values, score, _ = solve_moves(own, opp, max_empties, mode="scores", device=device)
+    _check_solved(score, "policy_report")
+    v, s = values.astype(np.int64), score.astype(np.int64)[:, None]
+    avail = v != nat.AZ_MOVES_NONE
+    has = avail.any(axis=1)
+    opt = (pi * (avail & (v == s))).sum(axis=1)[has]
+    wld = (pi * (avail & (np.sign(v) == np.sign(s)))).sum(axis=1)[has]
+    e = e[has]
+    by = {int(k): _mass(opt[e == k], wld[e == k]) for k in range(1, int(max_empties) + 1)}
+    return {"by_empties": by, "total": _mass(opt, wld)}

@@ -177,6 +177,20 @@ class OthelloGameNew(Game):
             raise RuntimeError("endgame search exceeded its node limit")
         return int(score[0]), int(best[0])
 
+    def solve_moves(self, state, player, max_empties=12):
+        """Exact value of every available action of `state` with `player` to move (not in the
+        reference): a dict action -> final disc difference for `player` when that action is
+        played and both sides play best afterwards (64 = pass, available only when `player`
+        has no placement and the opponent has one; empty when the game is over).  Raises as
+        `solve` does."""
+        own, opp = self._bb(state, player)
+        values, score, _ = nat.solve_moves_cpu(own, opp, max_empties)
+        if score[0] == nat.AZ_SOLVE_SKIPPED:
+            raise ValueError(f"position has more than {max_empties} empties")
+        if score[0] == nat.AZ_SOLVE_ABORTED:
+            raise RuntimeError("endgame search exceeded its node limit")
+        return {int(a): int(values[0, a]) for a in np.flatnonzero(values[0] != nat.AZ_MOVES_NONE)}
+
     def print_board(self, state, player, ply=None):
         """The reference's text rendering (envs/othello.py:459-498)."""
         lines = ["  a b c d e f g h"]

@@ -346,7 +346,8 @@ def _one_game(args_tuple):
 
 def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, stream_id=0,
                             d4_augment=False, dtype=torch.float32, group=None,
-                            sync_weights=True, pipelines=1, exact_endgame=0):
+                            sync_weights=True, pipelines=1, exact_endgame=0,
+                            exact_policy=False):
     """Batched replacement of Trainer.collect_self_play_games' pool (train.py:199-225):
     `num_games` games on the GPU, `n_slots` at a time (default min(games, 4096)), each
     searching with args['num_threads'] virtual-loss leaves per step (the reference's worker
@@ -376,15 +377,23 @@ def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, strea
     a few hundred roots of 15..20 empties that is several times slower than 16 host threads
     (the windowed solver's measured table); a caller to whom that matters keeps
     exact_endgame <= 14 here and labels engine sample rows itself with
-    endgame.relabel_rows(rows, E, device="cpu", wld=True)."""
+    endgame.relabel_rows(rows, E, device="cpu", wld=True).
+
+    exact_policy = True (needs exact_endgame > 0, else ValueError): the same rows also get an
+    exact policy target, uniform over the score-optimal moves (over the moves that keep the
+    win / draw / loss when E > 14), from the same one solver call that gives their z
+    (endgame.relabel_rows(policy=True)).  False (the default) leaves every pi as searched."""
     import torch.distributed as dist
+
+    if exact_policy and exact_endgame <= 0:
+        raise ValueError("exact_policy=True needs exact_endgame > 0")
 
     distributed = dist.is_available() and dist.is_initialized() and \
         dist.get_world_size(group) > 1
     if not distributed:
         rows = _local_rows(policy, args, num_games, n_slots, seed, stream_id, d4_augment, dtype,
                            pipelines)
-        return _rows_to_tuples(_exact_rows(rows, exact_endgame))
+        return _rows_to_tuples(_exact_rows(rows, exact_endgame, exact_policy))
     from dist_replay import allgather_samples, broadcast_state_dict
 
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -396,21 +405,24 @@ def collect_self_play_games(policy, args, num_games, n_slots=None, seed=0, strea
     mine = num_games // world + (1 if rank < num_games % world else 0)
     rows = _local_rows(policy, args, mine, n_slots, seed, stream_id + rank, d4_augment, dtype,
                        pipelines)
-    rows = _exact_rows(rows, exact_endgame)
+    rows = _exact_rows(rows, exact_endgame, exact_policy)
     pooled, _ = allgather_samples(rows, dev, group=group)
     return _rows_to_tuples({k: v.cpu().numpy() for k, v in pooled.items()})
 
 
-def _exact_rows(rows, exact_endgame):
+def _exact_rows(rows, exact_endgame, exact_policy=False):
     """The rows with exact endgame targets for positions of 1..exact_endgame empties (0: the
-    rows themselves)."""
+    rows themselves); exact_policy: their policy targets as well."""
     if exact_endgame <= 0 or len(rows["z"]) == 0:
         return rows
     from endgame import relabel_rows
 
     from az_native import AZ_SOLVE_MAX_EMPTIES
 
-    return relabel_rows(rows, exact_endgame, wld=exact_endgame > AZ_SOLVE_MAX_EMPTIES)[0]
+    wld = exact_endgame > AZ_SOLVE_MAX_EMPTIES
+    if exact_policy:
+        return relabel_rows(rows, exact_endgame, wld=wld, policy=True)[0]
+    return relabel_rows(rows, exact_endgame, wld=wld)[0]
 
 
 def _collective_device(group=None):

@@ -178,6 +178,40 @@ int oth_solve_deep_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, int3
                        int8_t* score_o, uint8_t* best_o, uint64_t* nodes_o, void* workspace,
                        size_t* workspace_bytes, void* stream);
 
+/* ---------------- the exact value of every move of a late position --------------------
+ * One call over a batch of roots (csrc/solve_moves.hip, host), own = side to move, values from
+ * the side to move's view.  Row i of values_o is 65 int8: entry a is the value of action a where a
+ * is available, AZ_MOVES_NONE elsewhere.  Available are the legal placements a < 64, and the
+ * pass (64) exactly when the side to move has no placement and the opponent has one.  The
+ * child of an available action is the position after it with the other side to move ((opp,
+ * own) after a pass); every child is one unsplit search of the windowed solver above.
+ *   AZ_MOVES_SCORES   child window (-65, 65): values[a] = -score(child), the exact disc
+ *                     difference the move leads to; score_o = their maximum, the root's score.
+ *   AZ_MOVES_WLD      child window (-1, 1): values[a] = -sign(score(child)) in {-1, 0, 1};
+ *                     score_o = their maximum.
+ *   AZ_MOVES_OPTIMAL  the root itself is searched in the full window first: s = score_o; then
+ *                     every child in (-s - 1, -s + 1): values[a] = -v(child), which is s
+ *                     exactly for every score-optimal move and, for every other move, a bound
+ *                     b with true value <= b <= s - 1.
+ * A terminal root (neither side can place): the row is all NONE, score_o the final difference,
+ * nodes 1.  A root with more than max_empties empties or own & opp != 0: all NONE, score_o
+ * AZ_SOLVE_SKIPPED, nodes 0.  node_limit applies per search; if any search of a root passes
+ * it, score_o is AZ_SOLVE_ABORTED and the whole row NONE (in OPTIMAL mode the children of a
+ * root whose own search aborted are not searched).  nodes_o (may be NULL) = 1 + the nodes of
+ * the root's searches, the root search of OPTIMAL mode included.  There is no device entry
+ * point of its own: endgame.solve_moves composes the same table on the device from
+ * oth_legal_gpu, oth_step_gpu and oth_solve_deep_gpu (split_plies = 0), which run the same
+ * searches, so values, scores and nodes agree with the host's bit for bit.
+ * max_empties outside 0..AZ_SOLVE_DEEP_MAX_EMPTIES or another mode is AZ_ERR_ARG. */
+#define AZ_MOVES_NONE (-128) /* action is not available in this position */
+#define AZ_MOVES_SCORES 0
+#define AZ_MOVES_WLD 1
+#define AZ_MOVES_OPTIMAL 2
+/* host pointers; reentrant and stateless */
+int oth_solve_moves_cpu(const uint64_t* own, const uint64_t* opp, int64_t n, int32_t max_empties,
+                        int32_t mode, uint64_t node_limit, int8_t* values_o /* n*65 */,
+                        int8_t* score_o, uint64_t* nodes_o);
+
 /* ---------------- exact values for late leaves of the search --------------------------
  * A pass between a leaf evaluation and the expansion that reads it (csrc/leaf_solve.hip).
  * Row r of nn_in is 64 floats in {-1, 0, +1}, the canonical planes of a leaf: own (the side
