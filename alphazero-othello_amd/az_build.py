@@ -24,7 +24,7 @@ SOURCES = ["csrc/board.hip", "csrc/engine.hip", "csrc/nn_fused.hip", "csrc/conv.
            "csrc/solve_moves.hip"]
 HEADERS = ["csrc/bitboard.h", "csrc/common.h", "csrc/philox.h", "csrc/heads_az.h",
            "csrc/solve.h", "csrc/search.h", "csrc/records.h", "csrc/solve_deep.h",
-           "../include/az_othello.h"]
+           "csrc/lane_search.h", "csrc/split_front.h", "../include/az_othello.h"]
 OUT = os.path.join(HERE, "libaz_othello.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function"]

@@ -15,11 +15,10 @@
 //   k_leaf_decode  one wave per row: lane i loads nn_in[row][i] (one coalesced 256-byte read),
 //                  two ballots give own / opp, and a row that qualifies appends itself to the
 //                  task list in the workspace with one atomic add.
-//   k_leaf_solve   k_solve_deep's shape: a lane takes one task at a time from a queue counter
-//                  and runs azd::init / azd::step on it, its frame stack in LDS laid out
-//                  [frame][field][lane], 11 frames (12 empties at most).  The task count is read
-//                  from the workspace; the grid follows `rows` (a step has a few thousand rows
-//                  and usually a few dozen tasks), not the device's size.
+//   k_leaf_solve   the lane kernel of lane_search.h over azd::init / azd::step with
+//                  k_solve_deep's frames, 11 of them (12 empties at most).  The task count is
+//                  read from the workspace; the grid follows `rows` (a step has a few thousand
+//                  rows and usually a few dozen tasks), not the device's size.
 //
 // Every loop is bounded: the lane loop by the task count, a search by node_limit nodes with at
 // most 20 probes before each; no lane waits for another.  The order in which rows enter the
@@ -30,10 +29,9 @@
 // stream): a 256-byte head {u32 queue, u32 tasks, ..., u64 stats[3] at byte 64}, then the
 // task list (int32 row, u64 own, u64 opp per row).  Each call re-arms queue and tasks; the
 // stats accumulate until the owner zeroes the workspace again.
-#include <stdexcept>
-
 #include "bitboard.h"
 #include "common.h"
+#include "lane_search.h"
 #include "solve_deep.h"
 
 namespace {
@@ -47,6 +45,9 @@ constexpr size_t kStatsOffset = 64;  // bytes
 static_assert(AZ_LEAF_SOLVE_MAX_EMPTIES == kLeafFrames + 1 &&
                   AZ_LEAF_SOLVE_MAX_EMPTIES <= azd::kMaxEmpties,
               "include/az_othello.h and csrc/leaf_solve.hip disagree");
+static_assert(azd::kRun == azl::kRun && azd::kDone == azl::kDone, "lane_search.h's states");
+
+using Stack = azl::LdsStack<kWave, 3, true>;  // k_solve_deep's
 
 struct LeafWs {
   uint32_t* ctr;    // [0] queue, [1] tasks
@@ -55,13 +56,11 @@ struct LeafWs {
   uint64_t *own, *opp;
 };
 
-size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-
-size_t carve(char* base, size_t rows, LeafWs* ws) {
+size_t layout(char* base, size_t rows, LeafWs* ws) {
   size_t off = kHeadBytes;
   auto take = [&](size_t bytes) {
     char* q = base ? base + off : nullptr;
-    off += align_up(bytes);
+    off += azl::align_up(bytes);
     return q;
   };
   LeafWs w;
@@ -108,54 +107,27 @@ __global__ __launch_bounds__(kDecodeBlock) void k_leaf_decode(const float* __res
   }
 }
 
-struct LdsStack {
-  uint64_t* w;  // [frame][3][kWave], this lane's column
-  uint32_t* p;  // [frame][kWave]
-  __device__ __forceinline__ void put(int f, uint64_t flips, uint64_t moves, uint64_t order,
-                                      uint32_t pk) {
-    w[(3 * f) * kWave] = flips;
-    w[(3 * f + 1) * kWave] = moves;
-    w[(3 * f + 2) * kWave] = order;
-    p[f * kWave] = pk;
-  }
-  __device__ __forceinline__ void get(int f, uint64_t& flips, uint64_t& moves, uint64_t& order,
-                                      uint32_t& pk) const {
-    flips = w[(3 * f) * kWave];
-    moves = w[(3 * f + 1) * kWave];
-    order = w[(3 * f + 2) * kWave];
-    pk = p[f * kWave];
-  }
-};
-
 __global__ __launch_bounds__(kWave) void k_leaf_solve(float* __restrict__ values, int max_empties,
                                                       uint64_t node_limit, LeafWs ws) {
-  __shared__ uint64_t w[kLeafFrames * 3 * kWave];
-  __shared__ uint32_t p[kLeafFrames * kWave];
-  LdsStack st{w + threadIdx.x, p + threadIdx.x};
-  const uint32_t n = ws.ctr[1];
-  azd::Search s;
-  s.state = azd::kDone;
+  __shared__ uint64_t lds[Stack::words(kLeafFrames)];
+  Stack st(lds, kLeafFrames);
   int32_t row = 0;
   unsigned long long solved = 0, limited = 0, nodes = 0;
-  for (;;) {
-    if (s.state != azd::kRun) {  // no work: take the next task, or leave
-      const uint32_t t = atomicAdd(&ws.ctr[0], 1u);
-      if (t >= n) break;
-      row = ws.row[t];
-      azd::init(s, ws.own[t], ws.opp[t], max_empties, -1, 1);
-    } else {
-      azd::step(s, st, node_limit, kLeafFrames);
-    }
-    if (s.state != azd::kRun) {
-      nodes += s.nodes;
-      if (s.score == azd::kAborted) {
-        ++limited;  // the net's value stays
-      } else {
-        ++solved;
-        values[row] = sign_value(s.score);
-      }
-    }
-  }
+  azl::run_lanes<azd::Search>(
+      st, ws.ctr[1], &ws.ctr[0], node_limit, kLeafFrames,
+      [&](azd::Search& s, uint32_t t) {
+        row = ws.row[t];
+        azd::init(s, ws.own[t], ws.opp[t], max_empties, -1, 1);
+      },
+      [&](const azd::Search& s) {
+        nodes += s.nodes;
+        if (s.score == azd::kAborted) {
+          ++limited;  // the net's value stays
+        } else {
+          ++solved;
+          values[row] = sign_value(s.score);
+        }
+      });
   auto* stats = reinterpret_cast<unsigned long long*>(ws.stats);
   if (solved) atomicAdd(&stats[0], solved);
   if (limited) atomicAdd(&stats[1], limited);
@@ -209,22 +181,15 @@ int az_leaf_solve_cpu(const float* nn_in, float* values, int64_t rows, int32_t m
 int az_leaf_solve_gpu(const float* nn_in, float* values, int64_t rows, int32_t max_empties,
                       uint64_t node_limit, void* workspace, size_t* workspace_bytes,
                       void* stream) {
-  const int rc = check_args("az_leaf_solve_gpu", rows, max_empties, node_limit);
+  int rc = check_args("az_leaf_solve_gpu", rows, max_empties, node_limit);
   if (rc != AZ_OK) return rc;
-  AZ_REQUIRE(workspace_bytes, AZ_ERR_ARG, "az_leaf_solve_gpu: null workspace_bytes");
-  const size_t need = carve(nullptr, (size_t)rows, nullptr);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return AZ_OK;
-  }
-  AZ_REQUIRE(*workspace_bytes >= need, AZ_ERR_ARG, "az_leaf_solve_gpu: workspace %zu < %zu bytes",
-             *workspace_bytes, need);
-  AZ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, AZ_ERR_ARG,
-             "az_leaf_solve_gpu: workspace must be 8-byte aligned");
-  if (rows == 0) return AZ_OK;
-  AZ_REQUIRE(nn_in && values, AZ_ERR_ARG, "az_leaf_solve_gpu: null buffer");
+  bool run = false;
+  rc = azl::claim_workspace("az_leaf_solve_gpu", "rows", rows, 0,
+                            layout(nullptr, (size_t)rows, nullptr), workspace, workspace_bytes,
+                            nn_in && values, &run);
+  if (rc != AZ_OK || !run) return rc;
   LeafWs ws;
-  carve(static_cast<char*>(workspace), (size_t)rows, &ws);
+  layout(static_cast<char*>(workspace), (size_t)rows, &ws);
   hipStream_t s = azc::as_stream(stream);
   AZ_HIP(hipMemsetAsync(ws.ctr, 0, 2 * sizeof(uint32_t), s));
   constexpr int kRowsPerBlock = kDecodeBlock / kWave;

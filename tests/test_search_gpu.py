@@ -193,6 +193,57 @@ def test_abort_code_matches_cpu(spread):
         assert (b2[~done] == 255).all()
 
 
+def test_a_level_that_overruns_aborts_its_root_and_leaves_nothing_behind(corpus):
+    """An unreachable board with 34 placements, one more than a level holds per root: alone
+    in its chunk it overruns level 1, a handled path with a defined result."""
+    own = np.array([0x0a11640000b40402], np.uint64)
+    opp = np.array([0x006602647002ba00], np.uint64)
+    assert (own & opp)[0] == 0 and popc(nat.legal_cpu(own, opp))[0] == 34
+    wv, wb, _ = nat.search_cpu(own, opp, 3, node_limit=LIMIT)
+    assert wv[0] > ABORTED and wb[0] < 64
+    need = ctypes.c_size_t(0)
+    nat.check(nat.lib.oth_search_gpu(None, None, 64, 3, LIMIT, 1, None, None, None, None,
+                                     ctypes.byref(need), None), "oth_search_gpu")
+    size1 = need.value
+    nat.check(nat.lib.oth_search_gpu(None, None, 1, 3, LIMIT, 2, None, None, None, None,
+                                     ctypes.byref(need), None), "oth_search_gpu")
+    ws = torch.empty(max(size1, need.value), dtype=torch.uint8, device="cuda")
+
+    def run(o, p, split):
+        n = len(o)
+        o_t, p_t = dev_i64(o), dev_i64(p)
+        v = torch.full((n + 2,), 99, dtype=torch.int16, device="cuda")
+        b = torch.full((n + 2,), 99, dtype=torch.uint8, device="cuda")
+        nd = torch.full((n + 2,), -1, dtype=torch.int64, device="cuda")
+        nat.check(nat.lib.oth_search_gpu(
+            nat.ptr(o_t), nat.ptr(p_t), n, 3, LIMIT, split, nat.ptr(v[1:]), nat.ptr(b[1:]),
+            nat.ptr(nd[1:]), nat.ptr(ws), ctypes.byref(ctypes.c_size_t(ws.numel())),
+            nat.stream_ptr()), "oth_search_gpu")
+        torch.cuda.synchronize()
+        v, b, nd = v.cpu().numpy(), b.cpu().numpy(), nd.cpu().numpy()
+        # the sentinels around the n results are untouched
+        assert v[0] == 99 and v[-1] == 99 and b[0] == 99 and b[-1] == 99
+        assert nd[0] == -1 and nd[-1] == -1
+        return v[1:-1], b[1:-1]
+
+    for split in (1, 2):
+        v, b = run(own, opp, split)
+        assert v[0] == ABORTED and b[0] == 255
+    # the same workspace, next call: 64 roots, nothing of the overrun is left
+    o64, p64 = corpus["own"][::577][:64], corpus["opp"][::577][:64]
+    assert len(o64) == 64
+    hv, hb, _ = nat.search_cpu(o64, p64, 3, node_limit=LIMIT)
+    v, b = run(o64, p64, 1)
+    assert (v == hv).all() and (b == hb).all()
+    # unsplit, and as one of two roots (the level holds 66 nodes: it fits), it is searched
+    v, b = run(own, opp, 0)
+    assert v[0] == wv[0] and b[0] == wb[0]
+    o2, p2 = np.concatenate([own, o64[:1]]), np.concatenate([opp, p64[:1]])
+    assert popc(nat.legal_cpu(o2, p2)).sum() <= 66
+    v, b = run(o2, p2, 1)
+    assert v[0] == wv[0] and b[0] == wb[0] and v[1] == hv[0] and b[1] == hb[0]
+
+
 def test_eval_whole_corpus(corpus):
     own = np.concatenate([corpus["own"], corpus["town"]])
     opp = np.concatenate([corpus["opp"], corpus["topp"]])
