@@ -186,37 +186,56 @@ def _random_step(own, opp, rng):
     return o, p, ok
 
 
-def reachable(plies):
+def _canon(own, opp):
+    import symmetry as sym_mod
+
+    o, p, _, _ = sym_mod.canon_cpu(own, opp)
+    return o, p
+
+
+def reachable(plies, symmetry=False):
     """The distinct positions (own, opp) after exactly `plies` placements from the initial
-    position that still have a placement."""
+    position that still have a placement.  symmetry=True: distinct up to the eight symmetries
+    of the square, each in canonical form (symmetry.canon): 1, 3, 14, 60, 322, 1,773 after
+    1..6 plies where there are 4, 12, 54, 236, 1,288, 7,092 positions."""
     own, opp = np.array([INIT_OWN], np.uint64), np.array([INIT_OPP], np.uint64)
+    if symmetry:
+        own, opp = _canon(own, opp)
     sh = np.arange(64, dtype=np.uint64)
     for _ in range(plies):
         lg = nat.legal_cpu(own, opp)
         par, act = np.nonzero(((lg[:, None] >> sh) & np.uint64(1)).astype(bool))
         own, opp = nat.make_move_cpu(own[par], opp[par], act.astype(np.uint8))
+        if symmetry:  # the children of one member of a class cover the children's classes
+            own, opp = _canon(own, opp)
         pair = np.unique(np.stack([own, opp], axis=1), axis=0)
         own, opp = np.ascontiguousarray(pair[:, 0]), np.ascontiguousarray(pair[:, 1])
     keep = nat.legal_cpu(own, opp) != 0
     return own[keep], opp[keep]
 
 
-def openings(n, plies, seed):
+def openings(n, plies, seed, symmetry=False):
     """n distinct start positions (own, opp, player): each reached by `plies` uniformly random
     legal placements from the initial position (plies even and at most 8: no game can have
     ended, and the first player is to move again), drawn with numpy.random.default_rng(seed);
     duplicates on (own, opp, player) are dropped and redrawn until n are distinct.  Raises
-    ValueError if fewer than n positions can be reached in `plies` plies."""
+    ValueError if fewer than n positions can be reached in `plies` plies.
+
+    symmetry=True: the same draws, but a position that is an image of an earlier one under
+    the symmetries of the square is a duplicate too, and the positions are returned in
+    canonical form (symmetry.canon) -- n different games, where the default may return mirror
+    images of one game."""
     n, plies = int(n), int(plies)
     if plies < 0 or plies > 8 or plies % 2:
         raise ValueError(f"plies={plies}: must be even and in 0..8")
     # 12, 236, 7,092 and 269,328 distinct positions at 2, 4, 6 and 8 plies: the small levels
     # are counted on every call, the last only for a request anywhere near its size
-    if plies <= 6 or n > 200000:
-        have = len(reachable(plies)[0])
+    # (up to symmetry at least an eighth of that: 3, 60, 1,773 and 33,666 or more)
+    if plies <= 6 or n > (25000 if symmetry else 200000):
+        have = len(reachable(plies, symmetry)[0])
         if n > have:
-            raise ValueError(f"openings: {plies} plies reach {have} distinct positions, "
-                             f"fewer than n={n}")
+            raise ValueError(f"openings: {plies} plies reach {have} distinct positions"
+                             f"{' up to symmetry' if symmetry else ''}, fewer than n={n}")
     rng = np.random.default_rng(seed)
     seen, out = set(), []
     while len(out) < n:
@@ -227,6 +246,8 @@ def openings(n, plies, seed):
             own, opp, had = _random_step(own, opp, rng)
             ok &= had
         ok &= nat.legal_cpu(own, opp) != 0
+        if symmetry:
+            own, opp = _canon(own, opp)
         for o, p in zip(own[ok].tolist(), opp[ok].tolist()):
             if (o, p) not in seen and len(out) < n:
                 seen.add((o, p))

@@ -326,13 +326,15 @@ def evaluate_models_batched(board_size, args, policy_state, best_policy_state, n
     return wa / n_matches, wb / n_matches
 
 
-def ladder(net, args, levels, n_matches, plies=8, seed=0, n_slots=None, device=None):
+def ladder(net, args, levels, n_matches, plies=8, seed=0, n_slots=None, device=None,
+           symmetry=False):
     """Absolute strength of `net` (nn.Module, inference form, or None = rollouts): play
     n_matches against AlphaBetaPlayer.level(L) for every L of `levels`, from
     openings(ceil(n_matches / 2), plies, seed), each opening once with each side moving
     first.  Returns {L: {"score": (wins + draws / 2) / n_matches, "wins", "draws",
-    "losses"}} from the net's side."""
-    ops = make_openings(-(-n_matches // 2), plies, seed)
+    "losses"}} from the net's side.  symmetry=True: the openings are pairwise different up
+    to the symmetries of the square (no mirror images of one game)."""
+    ops = make_openings(-(-n_matches // 2), plies, seed, symmetry=symmetry)
     out = {}
     for level in levels:
         arena = BatchedArena(net, AlphaBetaPlayer.level(level), args,

@@ -35,6 +35,7 @@ AZ_SOLVE_DEEP_MAX_EMPTIES = 20
 AZ_SEARCH_SKIPPED, AZ_SEARCH_ABORTED, AZ_SEARCH_MAX_DEPTH = -32768, -32767, 10
 AZ_REC_TERMINAL, AZ_REC_UNFINISHED, AZ_REC_ILLEGAL, AZ_REC_OVERFLOW = 0, 1, 2, 3
 AZ_REC_PASS_ROWS, AZ_REC_MAX_STRIDE, AZ_REC_MAX_ROWS = 1, 128, 128
+AZ_CANON_BAD = 255
 
 AZ_EVAL_EXTERNAL, AZ_EVAL_ROLLOUT = 0, 1
 AZ_RNG_DEVICE, AZ_RNG_INJECTED = 0, 1
@@ -162,6 +163,13 @@ SIGNATURES = {
     "oth_records_cpu": [_P, _I32, _P, _P, _P, _I64, _I32, _I32] + [_P] * 12,
     "oth_records_gpu": [_P, _I32, _P, _P, _P, _I64, _I32, _I32] + [_P] * 12 + [_P],
     "az_records_vote_gpu": [_P] * 4 + [_I64] + [_P] * 9,
+    "oth_canon_cpu": [_P, _P, _I64, _P, _P, _P, _P],
+    "oth_canon_gpu": [_P, _P, _I64, _P, _P, _P, _P, _P],
+    "az_copy16_probe_gpu": [_P, _P, _I64, _P],
+    "az_rows_d4_cpu": [_P, _P, _P, _P, _I64, _P, _P],
+    "az_rows_d4_gpu": [_P, _P, _P, _P, _I64, _P, _P, _P],
+    "az_rows_symmetrise_cpu": [_P, _P, _I64, _P],
+    "az_rows_symmetrise_gpu": [_P, _P, _I64, _P, _P],
     "az_rng_uniform_cpu": [_U64, _U32, _U32, _I64, _U32, _U32, _P],
     "az_rng_uniform_gpu": [_U64, _U32, _U32, _I64, _U32, _U32, _P, _P],
     "az_rng_dirichlet_gpu": [_U64, _U32, _U32, _I64, _U32, _D, _P, _P, _P],

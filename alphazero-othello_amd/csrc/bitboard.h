@@ -572,4 +572,116 @@ AZ_HD uint64_t d4(uint64_t x, int sym) {
 // Square index map of the same transform: out square of input square sq.
 AZ_HD int d4_square(int sq, int sym) { return 63 - __builtin_clzll(d4(1ull << sq, sym)); }
 
+// ---- canonical form under D4 ----------------------------------------------------------
+// d4_square by arithmetic: rot90 takes a stone on (r, c) to (7 - c, r) and fliplr takes it to
+// (r, 7 - c), so every symmetry is a row / column swap (odd k) followed by complements of the
+// two 3-bit coordinates.  No table and no bit scan of a transformed word.
+constexpr int d4_square_a(int sq, int sym) {
+  const int k = sym & 3, r = sq >> 3, c = sq & 7;
+  const int a = (k & 1) ? c : r, b = (k & 1) ? r : c;
+  const int rc = ((k ^ (k >> 1)) & 1) ? 7 : 0;             // k = 1, 2: complement the row
+  const int cc = (((k >> 1) ^ (sym >> 2)) & 1) ? 7 : 0;    // k = 2, 3, toggled by the flip
+  return ((a ^ rc) << 3) | (b ^ cc);
+}
+// The inverse symmetry: the two quarter turns are each other's, everything else its own.
+constexpr int d4_inverse(int sym) { return (sym & 5) == 1 ? (sym ^ 2) : sym; }
+// The square whose stone lands on `sq`: d4_square_a(d4_square_inv(sq, s), s) == sq.  Row
+// sym of train_gpu.pi_source_tables().
+constexpr int d4_square_inv(int sq, int sym) { return d4_square_a(sq, d4_inverse(sym)); }
+// t with d4(., t) = d4(d4(., u), s): a symmetry is known by where it sends squares 1 and 8
+constexpr int d4_compose(int s, int u) {
+  for (int t = 0; t < 8; ++t)
+    if (d4_square_a(1, t) == d4_square_a(d4_square_a(1, u), s) &&
+        d4_square_a(8, t) == d4_square_a(d4_square_a(8, u), s))
+      return t;
+  return -1;
+}
+// word s of the 8 x 8 table behind canon()'s stabiliser: three bits per `sym`, the t with
+// d4(., t) = d4(d4(., inverse(sym)), s)
+constexpr uint32_t stab_word(int s) {
+  uint32_t w = 0;
+  for (int u = 0; u < 8; ++u) w |= (uint32_t)d4_compose(s, d4_inverse(u)) << (3 * u);
+  return w;
+}
+
+// The eight images im[s] = d4(x, s) from one transpose, two bit reversals and four byte
+// swaps: with t = transpose(x), rot90 = flip_ud(t), rot180 = rev64(x), rot270 =
+// flip_lr(t), and flip_lr(y) = flip_ud(rev64(y)) (v_bfrev_b32 x 2 and v_perm_b32 x 2 on the
+// device).  Callers index `im` with constants only, so it stays in registers.
+AZ_HD void d4_images(uint64_t x, uint64_t* im) {
+  const uint64_t t = transpose(x), rx = rev64(x), rt = rev64(t);
+  im[0] = x;
+  im[1] = flip_ud(t);
+  im[2] = rx;
+  im[3] = flip_ud(rt);
+  im[4] = flip_ud(rx);
+  im[5] = rt;
+  im[6] = flip_ud(x);
+  im[7] = t;
+}
+
+struct Canon {
+  uint64_t own, opp;  // the smallest (d4(own, s), d4(opp, s)), own compared first
+  int sym;            // the smallest s that attains it
+  int stab;           // bit t: d4(., t) fixes the canonical pair (bit 0 always)
+};
+
+// The stabiliser comes from the set of s that attain the minimum, not from a second round
+// of transforms: d4(x, s) = c = d4(x, sym) means d4(., s) after the inverse of d4(., sym)
+// fixes c, and stab_word(s) holds that composition for every sym.
+AZ_HD Canon canon(uint64_t own, uint64_t opp) {
+  uint64_t a[8], b[8];
+  d4_images(own, a);
+  d4_images(opp, b);
+  Canon c{a[0], b[0], 0, 0};
+#pragma unroll
+  for (int s = 1; s < 8; ++s) {
+    const bool lt = a[s] < c.own || (a[s] == c.own && b[s] < c.opp);
+    c.own = lt ? a[s] : c.own;
+    c.opp = lt ? b[s] : c.opp;
+    c.sym = lt ? s : c.sym;
+  }
+  constexpr uint32_t kW[8] = {stab_word(0), stab_word(1), stab_word(2), stab_word(3),
+                              stab_word(4), stab_word(5), stab_word(6), stab_word(7)};
+  const int sh = 3 * c.sym;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const bool eq = a[s] == c.own && b[s] == c.opp;
+    c.stab |= eq ? (1 << ((kW[s] >> sh) & 7u)) : 0;
+  }
+  return c;
+}
+
+// The smallest square of sq's orbit under the symmetries of `stab`.
+AZ_HD int orbit_min(int sq, int stab) {
+  int m = sq;
+#pragma unroll
+  for (int t = 1; t < 8; ++t) {
+    const int q = d4_square_a(sq, t);
+    m = ((stab >> t) & 1) && q < m ? q : m;
+  }
+  return m;
+}
+
+// One entry of a row averaged over its stabiliser: v[t] = the row's value at
+// d4_square_inv(j, t).  The terms are taken in ascending t inside a fixed tree,
+// ((v0 + v2) + (v1 + v3)) + ((v4 + v6) + (v5 + v7)) with the absent ones left out: the
+// pairs are the cosets of the half turn (which every subgroup of order 4 or 8 contains) and
+// the halves those of the rotations, so a symmetry of `stab` permutes the tree's nodes and
+// only swaps operands of commutative sums.  The result is bit-identical on every square of
+// an orbit, which a plain left-to-right sum of four or eight terms is not.  The factor
+// 1 / popcount(stab) is a power of two for a subgroup.
+AZ_HD float symmetrise_one(const float* v, int stab) {
+  struct T {
+    float x;
+    bool has;
+  };
+  auto leaf = [&](int t) { return T{v[t], (bool)((stab >> t) & 1)}; };
+  auto add = [](T p, T q) { return T{p.has && q.has ? p.x + q.x : (p.has ? p.x : q.x), p.has || q.has}; };
+  const T s = add(add(add(leaf(0), leaf(2)), add(leaf(1), leaf(3))),
+                  add(add(leaf(4), leaf(6)), add(leaf(5), leaf(7))));
+  const int k = popc((uint64_t)(stab & 0xFF));
+  return k > 1 ? s.x * (1.0f / (float)k) : s.x;
+}
+
 }  // namespace azb

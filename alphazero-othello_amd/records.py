@@ -315,10 +315,13 @@ def keep_mask(ply, u, schedule=((8, 0.30), (16, 0.70))):
 
 # ---- dedup -----------------------------------------------------------------------------
 
-def vote_numpy(own, opp, act, z):
+def vote_numpy(own, opp, act, z, symmetry=False):
     """The host mirror of az_records_vote_gpu: (own, opp, act, z, count) with one row per
     distinct board in order of first occurrence, the most frequent action and outcome of its
-    group, ties to the value that appeared first."""
+    group, ties to the value that appeared first.  symmetry=True: per class of boards up to
+    symmetry (`canonical_rows` on the host first)."""
+    if symmetry:
+        own, opp, act = canonical_rows(np.asarray(own), opp, act, device="cpu")
     own = np.ascontiguousarray(own, np.uint64).reshape(-1)
     opp = np.ascontiguousarray(opp, np.uint64).reshape(-1)
     act = np.ascontiguousarray(act, np.uint8).reshape(-1)
@@ -355,10 +358,13 @@ def vote_numpy(own, opp, act, z):
     return own[f], opp[f], va[out_order], vz[out_order], count[out_order]
 
 
-def mean_numpy(own, opp, act, z):
+def mean_numpy(own, opp, act, z, symmetry=False):
     """The host form of dedup(how="mean"): per distinct board, in order of first occurrence,
     pi = the share of every action (float32 count / size) and z = the mean outcome
-    (float64 mean, cast to float32)."""
+    (float64 mean, cast to float32).  symmetry=True: per class of boards up to symmetry
+    (`canonical_rows` on the host first)."""
+    if symmetry:
+        own, opp, act = canonical_rows(np.asarray(own), opp, act, device="cpu")
     own = np.ascontiguousarray(own, np.uint64).reshape(-1)
     opp = np.ascontiguousarray(opp, np.uint64).reshape(-1)
     n = len(own)
@@ -425,11 +431,27 @@ def _pick(device, x):
         else torch.device("cpu")
 
 
-def vote(own, opp, act, z, device=None):
+def canonical_rows(own, opp, act, device=None):
+    """(own, opp, act) of every row in the canonical frame of its board (symmetry.canon): the
+    move goes through the board's symmetry and then to the smallest square of its orbit under
+    the symmetries that fix the canonical board, so mirror-image moves of a symmetric position
+    count as one.  Computed where dedup would run (`_pick`); types follow the input."""
+    import symmetry as sym_mod
+
+    dev = _pick(device, own)
+    o, p, s, stab = sym_mod.canon(own, opp, device=dev)
+    _, a = sym_mod.transform_rows(act=act, sym=s, stab=stab, device=dev)
+    return o, p, a
+
+
+def vote(own, opp, act, z, device=None, symmetry=False):
     """Majority-vote dedup (remove_conflicting_duplicates): (own, opp, act, z, count), one row
     per distinct board in order of first occurrence.  On the GPU (device None: when there is
     one, or where the tensors are) the kernel, on the host the NumPy mirror; NumPy in, NumPy
-    out, torch in, torch out."""
+    out, torch in, torch out.  symmetry=True votes per class of boards up to the symmetries of
+    the square (`canonical_rows` first; the boards come out canonical)."""
+    if symmetry:
+        own, opp, act = canonical_rows(own, opp, act, device)
     want_torch = isinstance(own, torch.Tensor)
     dev = _pick(device, own)
     if dev.type == "cuda":
@@ -450,13 +472,19 @@ def vote(own, opp, act, z, device=None):
     return res
 
 
-def dedup(own, opp, act, z, how="vote", device=None):
+def dedup(own, opp, act, z, how="vote", device=None, symmetry=False):
     """Collapse repeated boards.  Returns a dict: own, opp, count and
       how="vote": act uint8, z int8 -- the majority vote (`vote`);
       how="mean": pi float32 [m, 65] the empirical move distribution, z float32 the mean
                   outcome (on the GPU one-hot pi through replay.aggregate_rows with version
                   0, on the host `mean_numpy`);
-      how=None:   the rows as they are (act, z), count 1."""
+      how=None:   the rows as they are (act, z), count 1.
+    symmetry=True: boards that are images of each other under the symmetries of the square
+    are one board -- every row is first brought to its canonical frame (`canonical_rows`)."""
+    if how not in ("vote", "mean", None):
+        raise ValueError(f"how={how!r}: one of 'vote', 'mean', None")
+    if symmetry:
+        own, opp, act = canonical_rows(own, opp, act, device)
     if how == "vote":
         o, p, a, zz, c = vote(own, opp, act, z, device=device)
         return {"own": o, "opp": p, "act": a, "z": zz, "count": c}
@@ -464,8 +492,6 @@ def dedup(own, opp, act, z, how="vote", device=None):
         ones = torch.ones_like(act, dtype=torch.int32) if isinstance(act, torch.Tensor) \
             else np.ones(len(act), np.int32)
         return {"own": own, "opp": opp, "act": act, "z": z, "count": ones}
-    if how != "mean":
-        raise ValueError(f"how={how!r}: one of 'vote', 'mean', None")
     import replay as replay_mod
 
     want_torch = isinstance(own, torch.Tensor)

@@ -18,15 +18,32 @@ import torch
 import az_native as nat
 
 
-def aggregate_rows(own, opp, ver, pi, v):
+def aggregate_rows(own, opp, ver, pi, v, symmetry=False):
     """Device tensors in, device tensors out: own/opp int64 [n] (bit patterns), ver int32
     [n], pi float32 [n, 65], v float64 [n] -> (own, opp, ver, pi, v float32, count) of the
-    collapsed samples, in order of first occurrence."""
+    collapsed samples, in order of first occurrence.
+
+    symmetry=True merges rows whose boards are images of each other under the eight
+    symmetries of the square.  Every row is brought to its canonical form first: the boards
+    and pi through symmetry.canon / transform_rows, and pi then averaged over the symmetries
+    that fix the canonical board (symmetry.symmetrise) -- without that a row of a symmetric
+    position would still depend on which of its images was stored.  The same aggregation
+    then runs on the canonical rows.  Its per-entry arithmetic keeps bit-equal entries
+    bit-equal, so equivalent moves of an output row carry bit-equal targets, and the result
+    does not change by a bit when any input row is replaced by one of its images.  The
+    output boards are the canonical ones, in first-occurrence order of the classes; v and
+    count as before."""
     n = int(own.shape[0])
     dev = own.device
     cont = lambda t, dt: t.to(device=dev, dtype=dt).contiguous()  # noqa: E731
     own, opp = cont(own, torch.int64), cont(opp, torch.int64)
     ver, pi, v = cont(ver, torch.int32), cont(pi, torch.float32).reshape(n, 65), cont(v, torch.float64)
+    if symmetry:
+        import symmetry as sym_mod
+
+        own, opp, s, stab = sym_mod.canon_gpu(own, opp)
+        pi, _ = sym_mod.rows_d4_gpu(pi, None, s, None)
+        return aggregate_rows(own, opp, ver, sym_mod.symmetrise_gpu(pi, stab), v)
     m = max(n, 1)
     out = {"own": torch.empty(m, dtype=torch.int64, device=dev),
            "opp": torch.empty(m, dtype=torch.int64, device=dev),
@@ -48,9 +65,10 @@ def aggregate_rows(own, opp, ver, pi, v):
     return {key: t[:k] for key, t in out.items()}
 
 
-def aggregate_duplicates(replay_buffer, device=None):
+def aggregate_duplicates(replay_buffer, device=None, symmetry=False):
     """Trainer._aggregate_duplicates (train.py:142-173) on the GPU: same inputs, same three
-    lists, same order, same values."""
+    lists, same order, same values.  symmetry=True: one sample per class of boards up to the
+    symmetries of the square (aggregate_rows), the states in canonical form."""
     rows = list(replay_buffer)
     if not rows:
         return [], [], []
@@ -61,7 +79,8 @@ def aggregate_duplicates(replay_buffer, device=None):
     res = aggregate_rows(t(own.view(np.int64), torch.int64), t(opp.view(np.int64), torch.int64),
                          t(np.array([r[3] for r in rows], np.int32), torch.int32),
                          t(np.stack([np.asarray(r[1], np.float32) for r in rows]), torch.float32),
-                         t(np.array([float(r[2]) for r in rows], np.float64), torch.float64))
+                         t(np.array([float(r[2]) for r in rows], np.float64), torch.float64),
+                         symmetry=symmetry)
     o_own = res["own"].cpu().numpy().view(np.uint64)
     o_opp = res["opp"].cpu().numpy().view(np.uint64)
     boards = nat.unpack_np(o_own, o_opp, np.ones(len(o_own), np.int8)).reshape(-1, 8, 8)

@@ -797,6 +797,51 @@ int az_records_vote_gpu(const uint64_t* own, const uint64_t* opp, const uint8_t*
                         uint8_t* act_o, int8_t* z_o, int32_t* count_o, int32_t* n_out,
                         void* workspace, size_t* workspace_bytes, void* stream);
 
+/* ---- positions and rows up to the eight symmetries of the square (csrc/canon.hip) --------
+ * sym = k + 4 * flip as in oth_d4_*.  The canonical image of (own, opp) is the pair
+ * (d4(own, s), d4(opp, s)) that is smallest over s = 0..7, compared as unsigned 64-bit words,
+ * own first; sym_o = the smallest s that attains it; stab_o = the symmetries that fix the
+ * canonical pair (bit t set iff d4(., t) maps both of its boards to themselves; bit 0 always).
+ * Overlapping boards (own & opp != 0) are not transformed: the row's boards are copied,
+ * sym_o = AZ_CANON_BAD and stab_o = 0.  Outputs must not alias inputs. */
+#define AZ_CANON_BAD 255
+int oth_canon_cpu(const uint64_t* own, const uint64_t* opp, int64_t n, uint64_t* own_o,
+                  uint64_t* opp_o, uint8_t* sym_o, uint8_t* stab_o);
+/* device pointers, asynchronous on `stream`; any alignment (16-byte aligned board arrays and
+ * 2-byte aligned sym_o / stab_o take the two-positions-per-lane kernel).  Bit-identical to
+ * oth_canon_cpu. */
+int oth_canon_gpu(const uint64_t* own, const uint64_t* opp, int64_t n, uint64_t* own_o,
+                  uint64_t* opp_o, uint8_t* sym_o, uint8_t* stab_o, void* stream);
+
+/* Measurement probe: copies n16 16-byte words from src to dst (device, 16-byte aligned,
+ * distinct) with one float4 per lane on oth_canon_gpu's grid -- the copy rate the canon
+ * kernels are read against (scripts/bench_canon.py). */
+int az_copy16_probe_gpu(const void* src, void* dst, int64_t n16, void* stream);
+
+/* Apply every row's symmetry to its payload.  pi float [n, 65] -> pi_o: pi_o[d4_square(j,
+ * sym)] = pi[j] for j < 64, pi_o[64] = pi[64] (a gather through row sym of
+ * train_gpu.pi_source_tables()).  act uint8 [n] -> act_o: an action below 64 becomes
+ * d4_square(act, sym) and then, when `stab` is given, the smallest square of its orbit under
+ * the symmetries of stab; 64 (the pass) stays.  pi / pi_o and act / act_o may each be NULL
+ * (together); stab may be NULL; pi_o == pi is rejected.  A row with sym > 7 gets a pi_o row
+ * of NaN and act_o = AZ_CANON_BAD, as does an action above 64. */
+int az_rows_d4_cpu(const float* pi, const uint8_t* act, const uint8_t* sym, const uint8_t* stab,
+                   int64_t n, float* pi_o, uint8_t* act_o);
+int az_rows_d4_gpu(const float* pi, const uint8_t* act, const uint8_t* sym, const uint8_t* stab,
+                   int64_t n, float* pi_o, uint8_t* act_o, void* stream);
+
+/* Average every row over its stabiliser: for j < 64, pi_o[j] = the float32 sum over the set
+ * bits t of stab of pi[src_t(j)] (src_t = row t of pi_source_tables()), times 1 /
+ * popcount(stab), which is a power of two for a subgroup; pi_o[64] = pi[64].  The terms are
+ * added in ascending t inside the fixed tree ((t0 + t2) + (t1 + t3)) + ((t4 + t6) + (t5 +
+ * t7)), absent terms left out: for one or two terms that is the plain sum, and for four or
+ * eight it makes the result bit-identical on all squares of an orbit (a left-to-right sum is
+ * not).  A row with stab == 1 is copied; stab == 0 gives a row of NaN.  pi_o == pi is
+ * rejected. */
+int az_rows_symmetrise_cpu(const float* pi, const uint8_t* stab, int64_t n, float* pi_o);
+int az_rows_symmetrise_gpu(const float* pi, const uint8_t* stab, int64_t n, float* pi_o,
+                           void* stream);
+
 /* AlphaZeroNet's policy and value heads in one kernel (reference Models.py:196-221 with
  * BatchNorm folded, softmax of MCTS_model.py:319): h NHWC float [n_boards, 8, 8, C];
  * wpv [3][C] (rows: policy ch 0, policy ch 1, value) and bpv [3] the 1x1 convs; wpolT
