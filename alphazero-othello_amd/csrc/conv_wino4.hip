@@ -57,79 +57,15 @@
 #ifndef AZ_W4_STAMP
 #define AZ_W4_STAMP 0
 #endif
-// 1 (product): weight and input slices through buffer descriptors (wave-uniform chunk/step
-// offsets in soffset, no per-lane 64-bit address arithmetic), transform-row offsets and
-// signs compile-time per group (the group loop's last chunk pair peeled), the input scale
-// folded into the row combination; 0 = the round-2 loop (A/B builds)
-#ifndef AZ_W4_DIET
-#define AZ_W4_DIET 1
-#endif
 // experiment hooks (scripts/build_variants.py builds with bits set; results wrong):
 // 1 = no weight loads in the loop, 2 = no transform / input work in the loop, 4 = no MFMAs,
 // 8 = no LDS barrier in the loop, 16 = no A-fragment LDS reads, 32 = weight loads by the
 // first row tile's waves only (the other half reuses stale fragments), 64 = no input-slice
 // loads / LDS stores in the loop (the windows read stale slots), 128 = no global stores of a
-// non-residual conv's output, 256 = no global residual reads (the resident trunk's RES
-// epilogues), 512 = no resident-input write-out.  Product: 0.
+// non-residual conv's output, 256 = no global residual reads (the epilogues that do not stage
+// their residual in LDS: split3's), 512 = no resident-input write-out.  Product: 0.
 #ifndef AZ_W4_EXP
 #define AZ_W4_EXP 0
-#endif
-#ifndef AZ_W4_SCHED
-#define AZ_W4_SCHED 0
-#endif
-// wave priority (experiments): 1 = s_setprio 1 once for the younger half of an 8-wave
-// workgroup (waves 4-7), 2 = s_setprio 1 / 0 around each step's MFMA cluster
-#ifndef AZ_W4_PRIO
-#define AZ_W4_PRIO 0
-#endif
-// streaming cache hint (experiments): bit 0 = the input loads and the residual LDS-DMA
-// non-temporal (nt), bit 1 = the output stores non-temporal -- so the activations stream
-// past L2 instead of evicting the weight set every workgroup re-reads from it
-#ifndef AZ_W4_NT
-#define AZ_W4_NT 0
-#endif
-// timing proxy of a two-plane split (wrong numerics): 2 planes, 3 products
-#ifndef AZ_W4_PROXY2
-#define AZ_W4_PROXY2 0
-#endif
-// packed / mixed-precision forms of the transform's and fold's float ops (inline asm where
-// the compiler would split them); 0 = the plain vector expressions (A/B builds)
-#ifndef AZ_W4_PK
-#define AZ_W4_PK 1
-#endif
-// the lo word of put()'s fp16 split by the mixed-precision FMA (v_fma_mix*_f16); 0 = by
-// conversions and a subtraction (same bits)
-#ifndef AZ_W4_MIX
-#define AZ_W4_MIX AZ_W4_PK
-#endif
-// the remaining two-wide adds, products and FMAs of the input transform and the fold as one
-// packed instruction each (inline asm; the compiler emits about a third of them as two
-// scalar ops, profiles/r05_isa_mix.txt): 9 % less loop VALU but twice the hazard s_nops,
-// +0.3 % per launch (profiles/r05_conv_micro_ab.json); 0 = the plain vector expressions
-#ifndef AZ_W4_PK2
-#define AZ_W4_PK2 0
-#endif
-// the layer's last two chunks skip the pipeline's look-ahead past the end (clamped duplicates:
-// input slices, their LDS stores and window reads, the last chunk's weight steps, transform
-// and A fragments) -- none of it was ever used: -1.25 % per evaluation at B = 1,024, outputs
-// bit-identical (profiles/r04_conv_tail_ab.json); 0 = the uniform look-ahead (A/B builds)
-#ifndef AZ_W4_TAIL
-#define AZ_W4_TAIL 1
-#endif
-// the persistent trunk's layer input resident in LDS (see conv_body): 416.2-417.1 -> 368.7-371.3
-// us per B = 1,024 trunk + heads launch, configs[2] bench 104.1 -> 116.7 games/s, same box,
-// outputs bit-identical (profiles/r05_resident_ab.json); 0 = the per-chunk input slices with
-// the two-slice hand-off (AZ_W4_HANDOFF)
-#ifndef AZ_W4_RESIDENT
-#define AZ_W4_RESIDENT 1
-#endif
-// with the resident input: a residual conv stages its residual rows in X's odd rows, free
-// while the transform-grid row 3 (even input rows only) runs -- half 0 from the end of
-// group 2's seventh chunk, half 1 during group 3: 374.9-376.2 -> 344.4-345.9 us per B = 1,024
-// trunk + heads launch, configs[2] 116.9 -> 124.5 games/s, same box, bit-identical
-// (profiles/r05_resident_ab.json); 0 = read from global memory in the epilogue
-#ifndef AZ_W4_RXS
-#define AZ_W4_RXS 1
 #endif
 // boards per workgroup of the persistent trunk (az_trunk_wino4_gpu / _heads_gpu): 2 = two
 // workgroups per CU; 4 = one eight-wave workgroup per CU (with the resident input: X 128 KiB +
@@ -137,34 +73,17 @@
 #ifndef AZ_W4_TRUNK_BOARDS
 #define AZ_W4_TRUNK_BOARDS 2
 #endif
-// single-issue fp32 beside the MFMAs (bits): the two-wide adds, subtractions, products and
-// FMAs of 1 = the resident trunk's input transform (combine_kx, col_comb), 2 = the fold, 4 =
-// the epilogues' output pairs as two one-lane-wide instructions each instead of one
-// v_pk_*_f32; the same IEEE operations element by element, outputs bit-identical.  Bit 1 is
-// pinned by asm forms; bits 2 and 4 are plain expressions that -O3 pairs again unless the file
-// is built with -fno-slp-vectorize (scripts/build_variants.py NAME "-DAZ_W4_F32S=7
-// -fno-slp-vectorize").  B = 1,024 trunk + heads launch, builds interleaved on one box
-// (profiles/trunk_f32_issue_ab.json): bit 1 343.8 -> 338.6 us (the parent's round-to-round
-// range 1.2 us), configs[2] 129.6-130.3 -> 131.7-132.2 games/s; bit 2 alone 1.4 us slower, bit
-// 4 alone 1.9 us faster (inside the noise margin), all three 4.4 us faster -- less than bit 1
-// alone, so only bit 1 ships.  The per-layer kernels keep the packed transform (their code is
-// the same as before, instruction for instruction)
-#ifndef AZ_W4_F32S
-#define AZ_W4_F32S 1
-#endif
-// the epilogue's output pairs (2tx, 2tx + 1) as packed f32x2 (scale + bias in one v_pk_fma_f32,
-// the staged residual in one packed add): 411.0-411.5 -> 409.0-410.3 us per B = 1,024 trunk
-// + heads launch, same box (profiles/r05_conv_micro_ab.json); 0 = one element at a time
-#ifndef AZ_W4_EPI_PK
-#define AZ_W4_EPI_PK !(AZ_W4_F32S & 4)
-#endif
-// the persistent trunk's layer hand-off: a layer's epilogue also writes its output's first two
-// 16-channel slices (channels 0-31, held by the column-block-0 wave) into the input slots and
-// its per-board max |y| into LDS, so the next layer starts transforming without the global
-// round trip of those slices and of its input ranges (same values: bit-identical): 411.0-411.5
-// -> 408.0-410.1 us per launch (profiles/r05_conv_micro_ab.json); 0 = off
-#ifndef AZ_W4_HANDOFF
-#define AZ_W4_HANDOFF 1
+// Every other AZ_W4_* build switch this file once had guarded a form that was measured and
+// rejected or superseded (DESIGN.md §3 "Retired build switches" lists each with its outcome and
+// the commit that last carried it); the shipped value is now the only form, and an old -D must
+// not silently build the default
+#if defined(AZ_W4_DIET) || defined(AZ_W4_RESIDENT) || defined(AZ_W4_HANDOFF) ||                  \
+    defined(AZ_W4_RXS) || defined(AZ_W4_TAIL) || defined(AZ_W4_ZF) ||                            \
+    defined(AZ_W4_TRUNK_HEADS_EPI) || defined(AZ_W4_PK) || defined(AZ_W4_MIX) ||                 \
+    defined(AZ_W4_PK2) || defined(AZ_W4_F32S) || defined(AZ_W4_EPI_PK) || defined(AZ_W4_CMASK) || \
+    defined(AZ_W4_NT) || defined(AZ_W4_PRIO) || defined(AZ_W4_SCHED) || defined(AZ_W4_STAGGER) || \
+    defined(AZ_W4_PROXY2)
+#error "retired AZ_W4_* build switch; see DESIGN.md §3, Retired build switches"
 #endif
 
 namespace {
@@ -235,8 +154,7 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 template <int MODE_, int NRT_, int BOARDS_ = 4, int NC_ = 8, int NG_ = 4>
 struct W4 {
   static constexpr int C = 128, MODE = MODE_;
-  static constexpr int PLANES =
-      MODE == AZ_CONV_SPLIT3 ? (AZ_W4_PROXY2 ? 2 : 3) : (MODE == AZ_CONV_FP16X2 ? 2 : 1);
+  static constexpr int PLANES = MODE == AZ_CONV_SPLIT3 ? 3 : (MODE == AZ_CONV_FP16X2 ? 2 : 1);
   static constexpr bool SCALED = MODE == AZ_CONV_FP16X2;  // power-of-two operand scaling
   // NRT = MFMA row tiles per wave: 2 -> 4 waves (one per SIMD), each weight fragment feeds
   // both row tiles of its wave; 1 -> 8 waves (two per SIMD), row-tile partners request
@@ -259,11 +177,11 @@ struct W4 {
   // staged only where it fits beside the rest (not split3's three planes: its residual is
   // read from global memory in the epilogue)
   static constexpr bool RES_FITS = RES_OFF + RES_BYTES <= 160 * 1024 - 128;
-  // the persistent trunk's layer hand-off (AZ_W4_HANDOFF): each wave's per-board max |y|,
-  // [wave][board] floats after everything else
-  static constexpr int RNG_OFF = RES_FITS ? RES_OFF + RES_BYTES : RES_OFF;
-  static constexpr int LDS_BYTES = RNG_OFF + 128;
-  // the resident layout (AZ_W4_RESIDENT, the persistent trunk): V buffer 0, the layer's whole
+  // 128 bytes of slack after everything else: unused (the retired layer hand-off kept its
+  // ranges there), kept because the launches' dynamic LDS size is behaviour
+  static constexpr int SLACK_OFF = RES_FITS ? RES_OFF + RES_BYTES : RES_OFF;
+  static constexpr int LDS_BYTES = SLACK_OFF + 128;
+  // the resident layout (the persistent trunk): V buffer 0, the layer's whole
   // input X = [board][64 positions][C] fp32 (channel chunk slots swizzled by column pair,
   // xoff), V buffer 1 -- so a board-edge window's out-of-board rows and columns land in
   // finite words (X, or V's fp16 pairs, never an fp32 Inf / NaN pattern) and are masked
@@ -272,8 +190,7 @@ struct W4 {
   static constexpr int VPAD = BUF < 8192 ? 8192 : BUF;
   static constexpr int XOFF = VPAD, XBYTES = BOARDS * 64 * C * 4, V1R = VPAD + XBYTES;
   static constexpr int RSD_BYTES = 2 * VPAD + XBYTES;
-  static constexpr int TRUNK_LDS =
-      AZ_W4_RESIDENT && RSD_BYTES > LDS_BYTES ? RSD_BYTES : LDS_BYTES;
+  static constexpr int TRUNK_LDS = RSD_BYTES > LDS_BYTES ? RSD_BYTES : LDS_BYTES;
   static constexpr int LD_PER_THREAD = BOARDS * 64 * 4 / THREADS;  // 16-byte loads per chunk
   static constexpr int STEP_BYTES = PLANES * C * 32;  // weight bytes of one (chunk, point)
   static constexpr int CHUNKS = C / 16;
@@ -322,17 +239,8 @@ __host__ __device__ constexpr float grp_sa(int k) { return k == 2 ? -1.0f : 1.0f
 __host__ __device__ constexpr float grp_sb(int k) { return (k == 1 || k == 2) ? 1.0f : -1.0f; }
 
 // weight fragment of linear step q (chunk L = q / 4 = (group k, channel chunk c), point l)
-template <class G>
-__device__ __forceinline__ void load_b(Frag<G>& f, const char* wq, int wlane, int q) {
-  const int L = q >> 2, l = q & 3, k = L >> 3, c = L & 7;
-  const char* step = wq + (size_t)(c * 16 + 4 * k + l) * G::STEP_BYTES;
-#pragma unroll
-  for (int pl = 0; pl < G::PLANES; ++pl)
-    f.v[pl] = *reinterpret_cast<const Word8<G>*>(step + wlane + pl * G::C * 32);
-}
-
-// the same through the weights' buffer descriptor: the step's byte offset is wave-uniform
-// (soffset), the lane's (wlane) a fixed voffset
+// through the weights' buffer descriptor: the step's byte offset is wave-uniform (soffset),
+// the lane's (wlane) a fixed voffset -- no per-lane 64-bit address arithmetic
 template <class G>
 __device__ __forceinline__ void load_b(Frag<G>& f, __amdgpu_buffer_rsrc_t rw, int wlane, int q) {
   const int L = q >> 2, l = q & 3, k = L >> 3, c = L & 7;
@@ -367,18 +275,16 @@ __device__ __forceinline__ void mma(f32x16& acc, const Frag<G>& a, const Frag<G>
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v[0], b.v[0], z, 0, 0, 0);
   } else if constexpr (FIRST) {
     constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
-    constexpr int T0 = AZ_W4_PROXY2 ? 3 : 0;
     const f32x16 z = {};
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[PA[T0]], b.v[PB[T0]], z, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[PA[0]], b.v[PB[0]], z, 0, 0, 0);
 #pragma unroll
-    for (int t = T0 + 1; t < 6; ++t)
+    for (int t = 1; t < 6; ++t)
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[PA[t]], b.v[PB[t]], acc, 0, 0, 0);
   } else if constexpr (G::MODE == AZ_CONV_SPLIT3) {
     // smallest partial products first (x2y0, x1y1, x0y2, x1y0, x0y1, x0y0)
     constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
-    constexpr int T0 = AZ_W4_PROXY2 ? 3 : 0;  // proxy: the last three products only
 #pragma unroll
-    for (int t = T0; t < 6; ++t)
+    for (int t = 0; t < 6; ++t)
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[PA[t]], b.v[PB[t]], acc, 0, 0, 0);
   } else if constexpr (G::MODE == AZ_CONV_FP16X2) {
     // lo * hi, hi * lo, hi * hi (the lo * lo term is below fp32's rounding unit)
@@ -393,26 +299,15 @@ __device__ __forceinline__ void mma(f32x16& acc, const Frag<G>& a, const Frag<G>
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // the chunk-L slice of the workgroup's input (4 boards x 64 positions x 16 channels fp32):
-// LD_PER_THREAD coalesced 16-byte loads per thread into registers ...
-template <class G>
-__device__ __forceinline__ void load_in(f32x4 (&ld)[G::LD_PER_THREAD], const float* x,
-                                        const int (&goff)[G::LD_PER_THREAD], int L) {
-  const int c = L & 7;
-#pragma unroll
-  for (int j = 0; j < G::LD_PER_THREAD; ++j)
-    ld[j] = *reinterpret_cast<const f32x4*>(x + goff[j] + c * 16);
-}
-
-// the same through the input's buffer descriptor (goff in bytes; the chunk's channel offset
-// is wave-uniform)
+// LD_PER_THREAD coalesced 16-byte loads per thread into registers, through the input's buffer
+// descriptor (goff in bytes; the chunk's channel offset is wave-uniform) ...
 template <class G>
 __device__ __forceinline__ void load_in(f32x4 (&ld)[G::LD_PER_THREAD], __amdgpu_buffer_rsrc_t rx,
                                         const int (&goff)[G::LD_PER_THREAD], int L) {
   const int c = L & 7;
 #pragma unroll
   for (int j = 0; j < G::LD_PER_THREAD; ++j)
-    ld[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, goff[j], c * 64,
-                                                                             (AZ_W4_NT & 1) ? 2 : 0));
+    ld[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, goff[j], c * 64, 0));
 }
 
 // ... and into the slot's padded interior
@@ -466,7 +361,7 @@ __device__ __forceinline__ void make_rows(f32x2 (&rk)[4], const char* slot, int 
   combine_rows(rk, d, L);
 }
 
-// Compile-time group KK (AZ_W4_DIET): the window rows of slot PAR read with immediate LDS
+// Compile-time group KK (the whole-K kernels): the window rows of slot PAR read with immediate LDS
 // offsets from the lane's four column bases cb[b] (rbase + column slot), and combined with
 // the input scale folded in -- rk = vsc sa d_a0 + vsc sb d_a1 is vsc times the unscaled
 // row exactly (vsc is a power of two), so V and its split are bit-identical to scaling
@@ -482,52 +377,19 @@ __device__ __forceinline__ void read_rows_k(f32x2 (&d)[8], const char* lds, cons
   }
 }
 
-// a + b, a * b and fma(a, b, c) on f32x2 as one packed instruction (AZ_W4_PK2), else the
-// vector expressions; the same IEEE results element by element
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-#if AZ_W4_PK2
-  f32x2 r;
-  asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-#else
-  return a + b;
-#endif
-}
-__device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) {
-#if AZ_W4_PK2
-  f32x2 r;
-  asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-#else
-  return a * b;
-#endif
-}
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-#if AZ_W4_PK2
-  f32x2 r;
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-#else
-  return __builtin_elementwise_fma(a, b, c);
-#endif
-}
-
 // a - b on an f32x2 as ONE v_pk_add_f32 with b negated: the compiler splits a two-wide
 // fsub into two v_sub_f32 (and folds an fma by -1 back into that fsub); same IEEE
-// differences element by element
+// differences element by element.  (Two-wide adds, products and FMAs are the plain vector
+// expressions: the compiler packs most of them itself)
 __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-#if AZ_W4_PK
   f32x2 r;
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
   return r;
-#else
-  return a - b;
-#endif
 }
 
 // one single-issue fp32 instruction, as asm so that -O3 cannot pair two of them into a
-// v_pk_*_f32 again (AZ_W4_F32S bit 1: the transform's operands come from LDS reads and plain
-// VALU, never straight from an MFMA)
+// v_pk_*_f32 again (the resident trunk's input transform: its operands come from LDS reads and
+// plain VALU, never straight from an MFMA)
 __device__ __forceinline__ float s_add(float a, float b) {
   float r;
   asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -548,44 +410,34 @@ __device__ __forceinline__ float s_fma(float a, float b, float c) {
   asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
-// the transform's (bit 1) and the fold's (bit 2) two-wide operations: packed, or with the bit
-// set in AZ_W4_F32S one single-issue instruction per element (bit 1 pinned by the asm forms
-// above; bit 2 as plain expressions, which stay single only under -fno-slp-vectorize)
-template <int BIT>
+// the input transform's two-wide operations: SINGLE (the resident trunk's chunks) = one
+// single-issue instruction per element, else packed; the same IEEE results element by element
+template <bool SINGLE>
 __device__ __forceinline__ f32x2 f2_add(f32x2 a, f32x2 b) {
-  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_add(a.x, b.x), s_add(a.y, b.y)};
-  if constexpr ((AZ_W4_F32S & BIT) != 0) return f32x2{a.x + b.x, a.y + b.y};
-  return pk_add(a, b);
+  if constexpr (SINGLE) return f32x2{s_add(a.x, b.x), s_add(a.y, b.y)};
+  return a + b;
 }
-template <int BIT>
+template <bool SINGLE>
 __device__ __forceinline__ f32x2 f2_sub(f32x2 a, f32x2 b) {
-  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_sub(a.x, b.x), s_sub(a.y, b.y)};
-  if constexpr ((AZ_W4_F32S & BIT) != 0) return f32x2{a.x - b.x, a.y - b.y};
+  if constexpr (SINGLE) return f32x2{s_sub(a.x, b.x), s_sub(a.y, b.y)};
   return pk_sub(a, b);
 }
-template <int BIT>
-__device__ __forceinline__ f32x2 f2_mul(f32x2 a, float b) {
-  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_mul(a.x, b), s_mul(a.y, b)};
-  if constexpr ((AZ_W4_F32S & BIT) != 0) return f32x2{a.x * b, a.y * b};
-  return pk_mul(a, f32x2{b, b});
+// a * b and fma(a, b, c), b one scalar, single-issue (combine_kx is the resident trunk's only)
+__device__ __forceinline__ f32x2 s2_mul(f32x2 a, float b) {
+  return f32x2{s_mul(a.x, b), s_mul(a.y, b)};
 }
-// fma(a, b, c), b one scalar
-template <int BIT>
-__device__ __forceinline__ f32x2 f2_fma(f32x2 a, float b, f32x2 c) {
-  if constexpr ((AZ_W4_F32S & BIT & 1) != 0) return f32x2{s_fma(a.x, b, c.x), s_fma(a.y, b, c.y)};
-  if constexpr ((AZ_W4_F32S & BIT) != 0)
-    return f32x2{__builtin_fmaf(a.x, b, c.x), __builtin_fmaf(a.y, b, c.y)};
-  return pk_fma(a, f32x2{b, b}, c);
+__device__ __forceinline__ f32x2 s2_fma(f32x2 a, float b, f32x2 c) {
+  return f32x2{s_fma(a.x, b, c.x), s_fma(a.y, b, c.y)};
 }
 
 template <int KK>
 __device__ __forceinline__ void combine_k(f32x2 (&rk)[4], const f32x2 (&d)[8], float vsc) {
   const f32x2 fa = {grp_sa(KK) * vsc, grp_sa(KK) * vsc}, fb = {grp_sb(KK) * vsc, grp_sb(KK) * vsc};
 #pragma unroll
-  for (int b = 0; b < 4; ++b) rk[b] = pk_fma(fb, d[4 + b], pk_mul(fa, d[b]));
+  for (int b = 0; b < 4; ++b) rk[b] = __builtin_elementwise_fma(fb, d[4 + b], fa * d[b]);
 }
 
-// Resident input (AZ_W4_RESIDENT): byte offset in X of (board bd, position pos, channel ch):
+// Resident input: byte offset in X of (board bd, position pos, channel ch):
 // 16-channel chunk slots of 64 B, slot = chunk ^ ((column >> 1) & 3), so the four tiles of
 // a half-wave's window read (columns 2tx - 1 + b, tx = 0..3) hit four different bank groups
 template <class G>
@@ -623,10 +475,7 @@ __device__ __forceinline__ void read_rows_x(f32x2 (&d)[8], const char* lds, cons
 // Inf pairs of an absent board's overflowed rows), and coefficient x word could overflow to Inf
 // BEFORE the mask's x 0 -- NaN in the top-left window of a workgroup's first board, e.g. B = 5
 // boards with the last one's input range >= 64 alone in its workgroup (tests/
-// test_trunk_f32_issue_gpu.py).  0 = the masks applied after the combination (A/B builds)
-#ifndef AZ_W4_CMASK
-#define AZ_W4_CMASK 1
-#endif
+// test_trunk_f32_issue_gpu.py).
 // combine_k with the board-edge masks m = {top row valid, bottom row valid, left column valid,
 // right column valid} (0 / 1): a masked term is finite x 0, so the sums are the zero-padded
 // slot's (up to the sign of an exact zero)
@@ -636,46 +485,32 @@ __device__ __forceinline__ void combine_kx(f32x2 (&rk)[4], const f32x2 (&d)[8], 
   float fa_s = grp_sa(KK) * vsc, fb_s = grp_sb(KK) * vsc;
   if constexpr (KK == 0) fa_s *= m[0];  // window row 2ty - 1
   if constexpr (KK == 3) fb_s *= m[1];  // window row 2ty + 2
-#if AZ_W4_CMASK
   // the column masks in the coefficients of columns 2tx - 1 and 2tx + 2: a masked entry is
   // coefficient 0 x a finite word = 0 whatever the word's size
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     const float fa_b = b == 0 ? fa_s * m[2] : b == 3 ? fa_s * m[3] : fa_s;
     const float fb_b = b == 0 ? fb_s * m[2] : b == 3 ? fb_s * m[3] : fb_s;
-    rk[b] = f2_fma<1>(d[4 + b], fb_b, f2_mul<1>(d[b], fa_b));
+    rk[b] = s2_fma(d[4 + b], fb_b, s2_mul(d[b], fa_b));
   }
-#elif AZ_W4_F32S & 1
-#pragma unroll
-  for (int b = 0; b < 4; ++b) rk[b] = f2_fma<1>(d[4 + b], fb_s, f2_mul<1>(d[b], fa_s));
-  rk[0] = f2_mul<1>(rk[0], m[2]);  // window column 2tx - 1
-  rk[3] = f2_mul<1>(rk[3], m[3]);  // window column 2tx + 2
-#else
-  const f32x2 fa = {fa_s, fa_s}, fb = {fb_s, fb_s};
-#pragma unroll
-  for (int b = 0; b < 4; ++b) rk[b] = __builtin_elementwise_fma(fb, d[4 + b], fa * d[b]);
-  rk[0] = rk[0] * f32x2{m[2], m[2]};  // window column 2tx - 1
-  rk[3] = rk[3] * f32x2{m[3], m[3]};  // window column 2tx + 2
-#endif
 }
 
 // V at point (k, l) = (row k of B^T d) B: column combination l
-// BIT = 1: single-issue with AZ_W4_F32S bit 1 (the resident trunk's chunks); 0 = packed
-template <int l, int BIT = 0>
+// SINGLE: single-issue (the resident trunk's chunks); else packed
+template <int l, bool SINGLE = false>
 __device__ __forceinline__ f32x2 col_comb(const f32x2 (&rk)[4]) {
-  if constexpr (l == 0) return f2_sub<BIT>(rk[0], rk[2]);
-  if constexpr (l == 1) return f2_add<BIT>(rk[1], rk[2]);
-  if constexpr (l == 2) return f2_sub<BIT>(rk[2], rk[1]);
-  return f2_sub<BIT>(rk[1], rk[3]);
+  if constexpr (l == 0) return f2_sub<SINGLE>(rk[0], rk[2]);
+  if constexpr (l == 1) return f2_add<SINGLE>(rk[1], rk[2]);
+  if constexpr (l == 2) return f2_sub<SINGLE>(rk[2], rk[1]);
+  return f2_sub<SINGLE>(rk[1], rk[3]);
 }
 
 // split two transformed values into PLANES 16-bit words and store them in their slabs
 template <class G>
 __device__ __forceinline__ void put(char* slab, f32x2 v, float vsc) {
   if constexpr (G::MODE == AZ_CONV_FP16X2) {
-    const f32x2 vs = v * vsc;  // exact: a power of two (1 in the DIET path: folded away)
+    const f32x2 vs = v * vsc;  // exact: a power of two (1 where rk carries the scale: folded away)
     const f16x2 hi = __builtin_convertvector(vs, f16x2);
-#if AZ_W4_MIX
     // lo = RN16(vs - hi) per element by the mixed-precision FMA (hi read as f16, vs - hi
     // exact in f32, rounded once to f16): two v_fma_mix*_f16 instead of two f16 -> f32
     // conversions, the subtraction and a second packed conversion; bit-identical
@@ -686,11 +521,6 @@ __device__ __forceinline__ void put(char* slab, f32x2 v, float vsc) {
         : "v"(__builtin_bit_cast(uint32_t, hi)), "v"(vs.x), "v"(vs.y));
     *reinterpret_cast<f16x2*>(slab) = hi;
     *reinterpret_cast<uint32_t*>(slab + G::SLAB) = lo;
-#else
-    const f16x2 lo = __builtin_convertvector(vs - __builtin_convertvector(hi, f32x2), f16x2);
-    *reinterpret_cast<f16x2*>(slab) = hi;
-    *reinterpret_cast<f16x2*>(slab + G::SLAB) = lo;
-#endif
   } else if constexpr (G::MODE == AZ_CONV_SPLIT3) {
     const bf16x2 x0 = __builtin_convertvector(v, bf16x2);
     const f32x2 r1 = v - __builtin_convertvector(x0, f32x2);
@@ -698,15 +528,15 @@ __device__ __forceinline__ void put(char* slab, f32x2 v, float vsc) {
     const bf16x2 x2 = __builtin_convertvector(r1 - __builtin_convertvector(x1, f32x2), bf16x2);
     *reinterpret_cast<bf16x2*>(slab) = x0;
     *reinterpret_cast<bf16x2*>(slab + G::SLAB) = x1;
-    if (G::PLANES > 2) *reinterpret_cast<bf16x2*>(slab + 2 * G::SLAB) = x2;
+    *reinterpret_cast<bf16x2*>(slab + 2 * G::SLAB) = x2;
   } else {
     *reinterpret_cast<f16x2*>(slab) = __builtin_convertvector(v, f16x2);
   }
 }
 
-template <class G, int l, int BIT = 0>
+template <class G, int l, bool SINGLE = false>
 __device__ __forceinline__ void put_point(char* buf, const f32x2 (&rk)[4], int soff, float vsc) {
-  put<G>(buf + l * G::PLANES * G::SLAB + soff, col_comb<l, BIT>(rk), vsc);
+  put<G>(buf + l * G::PLANES * G::SLAB + soff, col_comb<l, SINGLE>(rk), vsc);
 }
 
 // group K's M (acc[l][t]) into the output accumulators Y[i][j][t]; K is a compile-time
@@ -720,38 +550,37 @@ __device__ __forceinline__ void fold(f32x16 (&acc)[4][G::NRT], f32x16 (&Y)[2][2]
     v[e] = x.x;
     v[e + 1] = x.y;
   };
-  auto sub = [](f32x2 a, f32x2 b) { return f2_sub<2>(a, b); };
 #pragma unroll
   for (int t = 0; t < G::NRT; ++t)
 #pragma unroll
     for (int e = 0; e < 16; e += 2) {
       const f32x2 m0 = get(acc[0][t], e), m1 = get(acc[1][t], e), m2 = get(acc[2][t], e),
                   m3 = get(acc[3][t], e);
-      const f32x2 t0 = f2_add<2>(f2_add<2>(m0, m1), m2), t1 = sub(sub(m1, m2), m3);
+      const f32x2 t0 = m0 + m1 + m2, t1 = pk_sub(pk_sub(m1, m2), m3);
       if constexpr (K == 0 && G::NG == 4) {
         set(Y[0][0][t], e, t0);
         set(Y[0][1][t], e, t1);
       } else if constexpr (K == 0) {  // NG = 1: Y starts at zero (rows of other workgroups)
-        set(Y[0][0][t], e, f2_add<2>(get(Y[0][0][t], e), t0));
-        set(Y[0][1][t], e, f2_add<2>(get(Y[0][1][t], e), t1));
+        set(Y[0][0][t], e, get(Y[0][0][t], e) + t0);
+        set(Y[0][1][t], e, get(Y[0][1][t], e) + t1);
       } else if constexpr (K == 1) {
-        set(Y[0][0][t], e, f2_add<2>(get(Y[0][0][t], e), t0));
-        set(Y[0][1][t], e, f2_add<2>(get(Y[0][1][t], e), t1));
+        set(Y[0][0][t], e, get(Y[0][0][t], e) + t0);
+        set(Y[0][1][t], e, get(Y[0][1][t], e) + t1);
         if constexpr (G::NG == 4) {
           set(Y[1][0][t], e, t0);
           set(Y[1][1][t], e, t1);
         } else {
-          set(Y[1][0][t], e, f2_add<2>(get(Y[1][0][t], e), t0));
-          set(Y[1][1][t], e, f2_add<2>(get(Y[1][1][t], e), t1));
+          set(Y[1][0][t], e, get(Y[1][0][t], e) + t0);
+          set(Y[1][1][t], e, get(Y[1][1][t], e) + t1);
         }
       } else if constexpr (K == 2) {
-        set(Y[0][0][t], e, f2_add<2>(get(Y[0][0][t], e), t0));
-        set(Y[0][1][t], e, f2_add<2>(get(Y[0][1][t], e), t1));
-        set(Y[1][0][t], e, sub(get(Y[1][0][t], e), t0));
-        set(Y[1][1][t], e, sub(get(Y[1][1][t], e), t1));
+        set(Y[0][0][t], e, get(Y[0][0][t], e) + t0);
+        set(Y[0][1][t], e, get(Y[0][1][t], e) + t1);
+        set(Y[1][0][t], e, pk_sub(get(Y[1][0][t], e), t0));
+        set(Y[1][1][t], e, pk_sub(get(Y[1][1][t], e), t1));
       } else {
-        set(Y[1][0][t], e, sub(get(Y[1][0][t], e), t0));
-        set(Y[1][1][t], e, sub(get(Y[1][1][t], e), t1));
+        set(Y[1][0][t], e, pk_sub(get(Y[1][0][t], e), t0));
+        set(Y[1][1][t], e, pk_sub(get(Y[1][1][t], e), t1));
       }
     }
   // materialise Y here: otherwise the compiler sinks the fold arithmetic past the next
@@ -776,17 +605,15 @@ struct St {
   f32x16 Y[2][2][G::NRT];
   int goff[G::LD_PER_THREAD], ldst[G::LD_PER_THREAD], rbase[G::TPT], cols[G::TPT], soff[G::TPT], aoff[G::NRT];
   float vsc[G::TPT];  // FP16X2: the item's board input scale 2^sv (1 otherwise)
-  int cbase[G::TPT][4];  // AZ_W4_DIET: the item's window column bases in an input slot
-  int xb[G::TPT][4];     // AZ_W4_RESIDENT: the item's window bases in X (read_rows_x)
-  float xm[G::TPT][4];   // AZ_W4_RESIDENT: its board-edge masks (combine_kx)
-  __amdgpu_buffer_rsrc_t rx, rw;  // input and weight descriptors (AZ_W4_DIET)
+  int cbase[G::TPT][4];  // the item's window column bases in an input slot (read_rows_k)
+  int xb[G::TPT][4];     // resident input: the item's window bases in X (read_rows_x)
+  float xm[G::TPT][4];   // resident input: its board-edge masks (combine_kx)
+  __amdgpu_buffer_rsrc_t rx, rw;  // input and weight descriptors
   int wlane, tid, b0, nb;
   int cs;             // first channel chunk of this workgroup's split (0 unless SPLIT)
   int g0;             // its transform-grid row (NG = 1; 0 otherwise)
   unsigned lds_res;   // LDS byte address of this wave's first residual piece
-  const float* x;
   const float* res;
-  const char* wq;
   char* lds;
 };
 
@@ -808,15 +635,10 @@ __device__ __forceinline__ int qmap(const St<G>& S, int vq) {
 // byte address lds_dst + 16 i.  Issued as asm so the compiler's vmcnt bookkeeping for the
 // weight and input loads is not collapsed to vmcnt(0) around it; its completion is waited
 // for explicitly (vmcnt(0)) before the barrier that precedes the reads
-#if AZ_W4_NT & 1
-#define AZ_W4_DMA_CPOL " nt"
-#else
-#define AZ_W4_DMA_CPOL ""
-#endif
 __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
   unsigned keep;
   asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" AZ_W4_DMA_CPOL
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
       "\n\ts_mov_b32 m0, %0"
       : "=&s"(keep)
       : "v"(gsrc), "s"(lds_dst));
@@ -840,7 +662,7 @@ __device__ __forceinline__ void res_dma(St<G>& S, int c) {
   }
 }
 
-// the resident trunk's residual staging (AZ_W4_RXS): segment c = (board c / 4, ty = c % 4) of
+// the resident trunk's residual staging: segment c = (board c / 4, ty = c % 4) of
 // half I -- row 2ty + I of the board, 8 positions x C fp32 = 4 KiB, one 16-byte piece per
 // thread -- into X's row 2ty + 1 of that board (linear [8][C]); S.lds_res = X + 1 KiB x wave
 template <class G, int I>
@@ -859,11 +681,12 @@ __device__ __forceinline__ void res_dma_x(St<G>& S, int c) {
 // four steps, the next chunk's transform into the other LDS buffer, the windows of the
 // chunk after that requested
 // KR / KS: the transform-grid rows of chunks v+1 (whose rows are combined here) and v+2
-// (whose windows are read at the end), when known at compile time (AZ_W4_DIET); -1 = from
-// the chunk map at run time
-// TAIL (AZ_W4_TAIL): 1 = the layer's second-to-last chunk (its input-slice look-ahead is past
-// the end), 2 = the last (everything after its own MFMAs is)
-// RSD (AZ_W4_RESIDENT): the layer input is resident in LDS -- no input-slice loads or stores,
+// (whose windows are read at the end), when known at compile time (the whole-K kernels); -1 =
+// from the chunk map at run time (the channel-split kernels)
+// TAIL: 1 = the layer's second-to-last chunk (its input-slice look-ahead is past the end), 2 =
+// the last (everything after its own MFMAs is): the clamped duplicates a uniform look-ahead would
+// fetch and transform there were never used
+// RSD: the layer input is resident in LDS -- no input-slice loads or stores,
 // the windows read from X, V buffer 1 after X
 // RDMA >= 0 (the resident trunk's residual staging): after this chunk's window reads, every
 // segment of residual half RDMA into X's odd rows (no window reads them from here to the
@@ -871,7 +694,7 @@ __device__ __forceinline__ void res_dma_x(St<G>& S, int c) {
 template <class G, int PAR, int STAGE, int KR = -1, int KS = -1, bool FIRST = false, int TAIL = 0,
           bool RSD = false, int RDMA = -1>
 __device__ __forceinline__ void run_chunk(St<G>& S, int v) {
-  constexpr bool CT = AZ_W4_DIET && KR >= 0 && KS >= 0;
+  constexpr bool CT = KR >= 0 && KS >= 0;
   static_assert(!RSD || CT, "the resident input needs the compile-time group rows");
   constexpr bool NO_IN = TAIL >= 1 || RSD, NO_NEXT = TAIL == 2;
   constexpr bool NO_WIN = TAIL >= 1;  // no window reads for chunk v + 2
@@ -896,10 +719,8 @@ __device__ __forceinline__ void run_chunk(St<G>& S, int v) {
     }
     const int slot = (4 * PAR + l) % G::RING;  // = step % RING (folds: l is unrolled)
     if (!(AZ_W4_EXP & 4)) {
-      if (AZ_W4_PRIO == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int t = 0; t < G::NRT; ++t) mma<G, FIRST>(S.acc[l][t], S.af[t], S.bf[slot]);
-      if (AZ_W4_PRIO == 2) __builtin_amdgcn_s_setprio(0);
     }
     if (l == 0 && !(AZ_W4_EXP & 2) && !NO_NEXT) {
       // chunk L+1's window rows (requested right after the previous barrier) combined
@@ -914,20 +735,12 @@ __device__ __forceinline__ void run_chunk(St<G>& S, int v) {
           combine_rows(S.rk[u], S.dr[u], Lr);
       }
     }
-    if (!(AZ_W4_EXP & 1) && (!(AZ_W4_EXP & 32) || S.tid < 256) && !(NO_NEXT && l + G::PD >= 4)) {
-      if constexpr (AZ_W4_DIET)
-        load_b<G>(S.bf[(slot + G::PD) % G::RING], S.rw, S.wlane, qmap<G>(S, v * 4 + l + G::PD));
-      else
-        load_b<G>(S.bf[(slot + G::PD) % G::RING], S.wq, S.wlane, qmap<G>(S, v * 4 + l + G::PD));
-    }
+    if (!(AZ_W4_EXP & 1) && (!(AZ_W4_EXP & 32) || S.tid < 256) && !(NO_NEXT && l + G::PD >= 4))
+      load_b<G>(S.bf[(slot + G::PD) % G::RING], S.rw, S.wlane, qmap<G>(S, v * 4 + l + G::PD));
     // the chunk-after-next's input slice at the chunk's first step: four steps of latency
     // cover before it is stored to LDS at the chunk's end
-    if (l == 0 && !(AZ_W4_EXP & 2) && !(AZ_W4_EXP & 64) && !NO_IN) {
-      if constexpr (AZ_W4_DIET)
-        load_in<G>(S.ld[set_l], S.rx, S.goff, Ll);
-      else
-        load_in<G>(S.ld[set_l], S.x, S.goff, Ll);
-    }
+    if (l == 0 && !(AZ_W4_EXP & 2) && !(AZ_W4_EXP & 64) && !NO_IN)
+      load_in<G>(S.ld[set_l], S.rx, S.goff, Ll);
     if constexpr (STAGE >= 0) {
       if constexpr (RSD) {
         if (l == 1) res_dma_x<G, STAGE>(S, L & 7);
@@ -947,18 +760,6 @@ __device__ __forceinline__ void run_chunk(St<G>& S, int v) {
 #pragma unroll
       for (int t = 0; t < G::NRT; ++t) S.af[t] = an[t];
     }
-#if AZ_W4_SCHED
-    // interleave: each MFMA followed by a share of the step's VALU and one LDS access, the
-    // global loads behind (compile-time instruction placement; the step ends at a barrier)
-#pragma unroll
-    for (int i = 0; i < 2 * G::NRT * (G::MODE == AZ_CONV_SPLIT3 ? 6 : 1); ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, AZ_W4_SCHED, 0);  // VALU
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
-    }
-    __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);  // VMEM read
-#endif
     __builtin_amdgcn_sched_barrier(0);
   }
   // slot (v+2) & 1 = v & 1 held chunk v's input, whose rows were formed in chunk v-1
@@ -984,14 +785,11 @@ __device__ __forceinline__ void run_chunk(St<G>& S, int v) {
 }
 
 // groups whose first chunk starts the accumulators itself (mma<G, true>): the whole-K
-// kernel with its first chunk pair peeled (AZ_W4_ZF, default on; 0 = the zeroing pass).
+// kernel with its first chunk pair peeled; the others zero them after each fold.
 // Not split3: its six-product body grew and measured 15 % slower peeled (63 -> 73 us)
-#ifndef AZ_W4_ZF
-#define AZ_W4_ZF 1
-#endif
 template <class G>
 constexpr bool zero_free() {
-  return AZ_W4_ZF && AZ_W4_DIET && !G::SPLIT && G::NC >= 4 && G::MODE != AZ_CONV_SPLIT3;
+  return !G::SPLIT && G::NC >= 4 && G::MODE != AZ_CONV_SPLIT3;
 }
 
 template <class G>
@@ -1025,10 +823,10 @@ __device__ __forceinline__ void run_group(St<G>& S) {
       run_chunk<G, 0, STAGE, K, K, false, 0, RSD>(S, KV * G::NC + c);
       run_chunk<G, 1, STAGE, K, K, false, 0, RSD>(S, KV * G::NC + c + 1);
     }
-    constexpr int T1 = AZ_W4_TAIL && K == 3 ? 1 : 0, T2 = AZ_W4_TAIL && K == 3 ? 2 : 0;
+    constexpr int T1 = K == 3 ? 1 : 0, T2 = K == 3 ? 2 : 0;  // the layer's last two chunks
     run_chunk<G, 0, STAGE, K, KN, false, T1, RSD, RDMA>(S, KV * G::NC + G::NC - 2);
     run_chunk<G, 1, STAGE, KN, KN, false, T2, RSD>(S, KV * G::NC + G::NC - 1);
-  } else if constexpr (AZ_W4_DIET && !G::SPLIT) {
+  } else if constexpr (!G::SPLIT) {  // whole K, not zero-free (split3): the last pair peeled
     constexpr int KN = K + 1;
 #pragma unroll 1
     for (int c = 0; c < G::NC - 2; c += 2) {
@@ -1037,7 +835,7 @@ __device__ __forceinline__ void run_group(St<G>& S) {
     }
     run_chunk<G, 0, STAGE, K, KN>(S, KV * G::NC + G::NC - 2);
     run_chunk<G, 1, STAGE, KN, KN>(S, KV * G::NC + G::NC - 1);
-  } else {
+  } else {  // a channel split of 2 or 4 chunks: the group rows from the chunk map
 #pragma unroll 1
     for (int c = 0; c < G::NC; c += 2) {
       run_chunk<G, 0, STAGE>(S, KV * G::NC + c);
@@ -1059,9 +857,10 @@ struct Epi {
 // output half I (rows 2ty + I): accumulator element e of row tile rt = tile 32rt + (e&3) +
 // 8(e>>2) + 4h, column co; Y[I][j] = output (2ty + I, 2tx + j); + bias (+ the staged
 // residual), ReLU, store, and the boards' max |y|
-// RST: the residual is staged in LDS (else read from global memory); NOY: the output is not
-// stored to global memory (the resident trunk's conv1 outputs: only the next conv reads them,
-// from X)
+// RST: the residual is staged in LDS -- RXS: in X's odd rows (the resident trunk), else in the
+// RES_OFF area -- and without RST read from global memory (split3: no LDS left to stage it);
+// NOY: the output is not stored to global memory (the resident trunk's conv1 outputs: only the
+// next conv reads them, from X)
 template <class G, int I, bool RES, bool RELU, bool HEADS = false, bool KEEP = false,
           bool RST = G::RES_FITS, bool NOY = false, bool RXS = false>
 __device__ __forceinline__ void epilogue(St<G>& S, Epi<G>& E, const float* __restrict__ res,
@@ -1074,7 +873,6 @@ __device__ __forceinline__ void epilogue(St<G>& S, Epi<G>& E, const float* __res
       const int T = 32 * (rt0 + t) + (e & 3) + 8 * (e >> 2) + 4 * h;
       const int bd = T >> 4, ty = (T >> 2) & 3, tx = T & 3;
       if (bd >= S.nb) continue;
-#if AZ_W4_EPI_PK
       // the output pair (2tx, 2tx + 1) of row 2ty + I shares its scale, bias and column: one
       // v_pk_fma_f32 for scale + bias (the power-of-two scaling is exact, so the fused form
       // rounds like the product then the sum), one packed residual add
@@ -1104,7 +902,7 @@ __device__ __forceinline__ void epilogue(St<G>& S, Epi<G>& E, const float* __res
         E.bmax[2 * t + (e >> 3)] = fmaxf(E.bmax[2 * t + (e >> 3)], fmaxf(fabsf(v.x), fabsf(v.y)));
         continue;
       }
-#endif
+      // element by element: the fused heads' inputs, the unscaled modes, split3's residual
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int pos = (2 * ty + I) * 8 + 2 * tx + j;
@@ -1119,11 +917,7 @@ __device__ __forceinline__ void epilogue(St<G>& S, Epi<G>& E, const float* __res
         if constexpr (HEADS) {  // kept for the fused heads (heads_epilogue), not stored
           S.Y[I][j][t][e] = v;
         } else {
-          if constexpr (NOY) {
-          } else if constexpr ((AZ_W4_NT & 2) != 0)
-            __builtin_nontemporal_store(v, &y[((size_t)(S.b0 + bd) * 64 + pos) * C + E.co]);
-          else
-            y[((size_t)(S.b0 + bd) * 64 + pos) * C + E.co] = v;
+          if constexpr (!NOY) y[((size_t)(S.b0 + bd) * 64 + pos) * C + E.co] = v;
           if constexpr (KEEP) S.Y[I][j][t][e] = v;
           E.bmax[2 * t + (e >> 3)] = fmaxf(E.bmax[2 * t + (e >> 3)], fabsf(v));
         }
@@ -1193,18 +987,14 @@ __device__ __forceinline__ void heads_epilogue(St<G>& S, const HeadsOut& ho, int
 
 // One conv of this workgroup's boards (the whole kernel of k_conv3x3_wino4; the persistent
 // trunk k_trunk_wino4 runs it once per layer on the same boards).
-// HIN / HOUT (AZ_W4_HANDOFF, the persistent trunk's layers): HIN = the input's first two
-// slices are already in the input slots and its per-board ranges in LDS (written by the
-// previous layer's HOUT epilogue, ordered by the layer fence); HOUT = write them for the next
-// layer.  Two-board, one-row-tile form only (the trunk's).
-// RSD (AZ_W4_RESIDENT, the persistent trunk's layers instead of the hand-off): the layer's whole
-// input is resident in LDS (X, G::XOFF) -- XFILL = load it from x first (a launch's first
-// conv), else the previous layer wrote it; XOUT = write this layer's output there after the
-// last window read (ordered by the layer fence).  No input slices are loaded or stored per
-// chunk; the residual is read from global memory in the epilogue (no LDS left to stage it);
-// a conv1 output with XOUT is not stored to global memory at all (only the next conv reads it).
-template <class G, bool RES, bool RELU, bool HEADS = false, bool LAUNDER = false,
-          bool HIN = false, bool HOUT = false, bool RSD = false, bool XFILL = false,
+// RSD (the persistent trunk's layers, `layer` of the launch): the layer's whole input is
+// resident in LDS (X, G::XOFF) -- XFILL = load it from x first (a launch's first conv), else
+// the previous layer wrote it; XOUT = write this layer's output there after the last window
+// read (ordered by the layer fence).  No input slices are loaded or stored per chunk; a
+// residual is staged in X's odd rows while transform-grid row 3 (even input rows only) runs
+// (res_dma_x); a conv1 output with XOUT is not stored to global memory at all (only the next
+// conv reads it).
+template <class G, bool RES, bool RELU, bool HEADS = false, bool RSD = false, bool XFILL = false,
           bool XOUT = false>
 __device__ __forceinline__ void conv_body(
     const float* __restrict__ x, const char* __restrict__ wq, const float* __restrict__ bias,
@@ -1212,13 +1002,9 @@ __device__ __forceinline__ void conv_body(
     float* __restrict__ in_absmax, float* __restrict__ out_absmax, HeadsOut ho,
     int layer = 0) {
   constexpr int C = G::C;
-  static_assert(!(HIN || HOUT) || (G::BOARDS == 2 && G::NRT == 1 && G::IPD == 1 && G::SCALED &&
-                                   !G::SPLIT && LAUNDER),
-                "the layer hand-off is the persistent two-board fp16x2 trunk's");
   static_assert(!(RSD || XFILL || XOUT) ||
-                    (RSD && !HIN && !HOUT && (G::BOARDS == 2 || G::BOARDS == 4) && G::NRT == 1 &&
-                     (G::SCALED || G::MODE == AZ_CONV_FP16) &&
-                     !G::SPLIT && LAUNDER && AZ_W4_DIET && C == 128),
+                    (RSD && (G::BOARDS == 2 || G::BOARDS == 4) && G::NRT == 1 &&
+                     (G::SCALED || G::MODE == AZ_CONV_FP16) && !G::SPLIT && C == 128),
                 "the resident input is the persistent two-board fp16x2 / fp16 trunk's");
   constexpr bool NOY = RSD && XOUT && !RES && !HEADS;
 
@@ -1227,19 +1013,15 @@ __device__ __forceinline__ void conv_body(
   W4T_STAMP(layer, 0);
   St<G> S;
   S.lds = reinterpret_cast<char*>(lds4);
-  S.x = x;
-  S.wq = wq;
-  if constexpr (AZ_W4_DIET) {
-    const long long xb = (long long)n_boards * 64 * C * 4;
-    S.rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, xb < 0x7fffffff ? (int)xb : 0x7fffffff,
-                                             0x00020000);
-    S.rw = __builtin_amdgcn_make_buffer_rsrc((void*)wq, 0, G::QSTEPS * G::STEP_BYTES, 0x00020000);
-  }
+  const long long xbytes = (long long)n_boards * 64 * C * 4;
+  S.rx = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)x, 0, xbytes < 0x7fffffff ? (int)xbytes : 0x7fffffff, 0x00020000);
+  S.rw = __builtin_amdgcn_make_buffer_rsrc((void*)wq, 0, G::QSTEPS * G::STEP_BYTES, 0x00020000);
   S.res = res;
   // laundered: the persistent trunk runs this body once per layer, and everything derived
   // from the lane index hoisted out of its layer loop would stay live across both bodies
   int tid = threadIdx.x;
-  if constexpr (LAUNDER) asm volatile("" : "+v"(tid));
+  if constexpr (RSD) asm volatile("" : "+v"(tid));
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cb = wave & 3, rt0 = G::NRT == 1 ? wave >> 2 : 0;
@@ -1247,19 +1029,6 @@ __device__ __forceinline__ void conv_body(
   const int col0 = 32 * cb;
   const int b0 = blockIdx.x * G::BOARDS;
   const int nb = n_boards - b0 < G::BOARDS ? n_boards - b0 : G::BOARDS;
-  // the input range of board bd (< nb): from the previous layer's LDS hand-off (the max of
-  // its waves' maxima: the value the buffer's atomics hold), else the buffer
-  auto in_range = [&](int bd) -> float {
-    if constexpr (HIN) {
-      const float* rng = reinterpret_cast<const float*>(S.lds + G::RNG_OFF);
-      float m = rng[bd];
-#pragma unroll
-      for (int w = 1; w < G::WAVES; ++w) m = fmaxf(m, rng[w * 4 + bd]);
-      return m;
-    } else {
-      return in_absmax[b0 + bd];
-    }
-  };
   S.tid = tid;
   S.b0 = b0;
   S.nb = nb;
@@ -1291,7 +1060,7 @@ __device__ __forceinline__ void conv_body(
     if constexpr (G::SCALED) {
       // |V| <= 4 max |x| < 2^(e+2): scaled by 2^(13-e), the transformed inputs stay below
       // 2^15 (fp16's largest power of two)
-      const int e = frexp_exp(bd < nb ? in_range(bd) : 0.0f);
+      const int e = frexp_exp(bd < nb ? in_absmax[b0 + bd] : 0.0f);
       S.vsc[u] = ldexpf(1.0f, 13 - e);
     }
     if constexpr (RSD) {
@@ -1319,15 +1088,13 @@ __device__ __forceinline__ void conv_body(
     const int P = (P0 & ~3) | ((P0 & 1) << 1) | ((P0 >> 1) & 1);
     const int bd = P >> 6, pos = P & 63;
     const int bs = bd < nb ? bd : nb - 1;
-    S.goff[j] = (((b0 + bs) * 64 + pos) * C + 4 * q) * (AZ_W4_DIET ? 4 : 1);  // DIET: bytes
+    S.goff[j] = (((b0 + bs) * 64 + pos) * C + 4 * q) * 4;  // bytes (the descriptor's voffset)
     S.ldst[j] = bd * G::IN_BOARD + ((pos >> 3) + 1) * G::IN_ROW + col_slot((pos & 7) + 1) * 64 + q * 16;
   }
 
   // ---- prologue: zero both input slots (their borders stay zero), chunk 0 and 1 slices and
   // the first weight steps in flight together; chunk 0 transformed into V buffer 0
-  // (the persistent trunk's later layers: the borders are still zero -- interior stores never
-  // touch them -- and the layer fence ordered the previous layer's reads)
-  const bool fill = !LAUNDER || layer == 0;
+  // (the resident trunk: X instead of the slots, filled by a launch's first conv only)
   if constexpr (RSD) {
     if constexpr (XFILL) {
       // V buffers zeroed (a board-edge window reads some of their words: finite from here on),
@@ -1365,43 +1132,20 @@ __device__ __forceinline__ void conv_body(
       read_rows_x<G, 0>(d, S.lds, S.xb[u], 0);
       combine_kx<0>(S.rk[u], d, S.vsc[u], S.xm[u]);
     }
-  } else if constexpr (HIN) {
-    // chunks 0 and 1 are in the slots already (the previous layer's hand-off, ordered by the
-    // layer fence); chunk 2's slice (stored at the end of chunk 0) and the first weight steps
-    char* in0 = S.lds + G::IN_OFF;
-    load_in<G>(S.ld[0], S.rx, S.goff, lmap<G>(S, 2));
-#pragma unroll
-    for (int i = 0; i < G::PD; ++i) load_b<G>(S.bf[i], S.rw, S.wlane, qmap<G>(S, i));
-#pragma unroll
-    for (int u = 0; u < G::TPT; ++u) make_rows<G>(S.rk[u], in0, S.rbase[u], S.cols[u], lmap<G>(S, 0));
   } else {
     char* in0 = S.lds + G::IN_OFF;
-    if (fill)
-      for (int i = tid * 16; i < 2 * G::IN_SLOT; i += G::THREADS * 16)
-        *reinterpret_cast<f32x4*>(in0 + i) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = tid * 16; i < 2 * G::IN_SLOT; i += G::THREADS * 16)
+      *reinterpret_cast<f32x4*>(in0 + i) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     f32x4 ld0[G::LD_PER_THREAD], ld1[G::LD_PER_THREAD];
-    if constexpr (AZ_W4_DIET) {
-      load_in<G>(ld0, S.rx, S.goff, lmap<G>(S, 0));
-      load_in<G>(G::IPD == 1 ? S.ld[0] : ld1, S.rx, S.goff, lmap<G>(S, 1));
-      if (G::IPD == 2) load_in<G>(S.ld[0], S.rx, S.goff, lmap<G>(S, 2));
+    load_in<G>(ld0, S.rx, S.goff, lmap<G>(S, 0));
+    load_in<G>(G::IPD == 1 ? S.ld[0] : ld1, S.rx, S.goff, lmap<G>(S, 1));
+    if (G::IPD == 2) load_in<G>(S.ld[0], S.rx, S.goff, lmap<G>(S, 2));  // stored at the end of chunk 0
 #pragma unroll
-      for (int i = 0; i < G::PD; ++i) load_b<G>(S.bf[i], S.rw, S.wlane, qmap<G>(S, i));
-    } else {
-      load_in<G>(ld0, x, S.goff, lmap<G>(S, 0));
-      load_in<G>(G::IPD == 1 ? S.ld[0] : ld1, x, S.goff, lmap<G>(S, 1));
-      if (G::IPD == 2) load_in<G>(S.ld[0], x, S.goff, lmap<G>(S, 2));  // stored at the end of chunk 0
-#pragma unroll
-      for (int i = 0; i < G::PD; ++i) load_b<G>(S.bf[i], wq, S.wlane, qmap<G>(S, i));
-    }
-    if (fill) lds_barrier();  // the zero fill before any interior store
+    for (int i = 0; i < G::PD; ++i) load_b<G>(S.bf[i], S.rw, S.wlane, qmap<G>(S, i));
+    lds_barrier();  // the zero fill before any interior store
     store_in<G>(in0, ld0, S.ldst);
     store_in<G>(in0 + G::IN_SLOT, G::IPD == 1 ? S.ld[0] : ld1, S.ldst);
-    if (G::IPD == 1) {  // stored at the end of chunk 0
-      if constexpr (AZ_W4_DIET)
-        load_in<G>(S.ld[0], S.rx, S.goff, lmap<G>(S, 2));
-      else
-        load_in<G>(S.ld[0], x, S.goff, lmap<G>(S, 2));
-    }
+    if (G::IPD == 1) load_in<G>(S.ld[0], S.rx, S.goff, lmap<G>(S, 2));  // stored at the end of chunk 0
     lds_barrier();
 #pragma unroll
     for (int u = 0; u < G::TPT; ++u) make_rows<G>(S.rk[u], in0, S.rbase[u], S.cols[u], lmap<G>(S, 0));
@@ -1440,14 +1184,12 @@ __device__ __forceinline__ void conv_body(
 #pragma unroll
     for (int i = 0; i < 2 * G::NRT; ++i) {
       const int bd = 2 * rt0 + i;
-      const int e = frexp_exp(bd < nb ? in_range(bd) : 0.0f);
+      const int e = frexp_exp(bd < nb ? in_absmax[b0 + bd] : 0.0f);
       E.unsc[i] = ldexpf(1.0f, -(su + 13 - e));
     }
   }
   W4_STAMP(1);
   W4T_STAMP(layer, 1);
-  if (AZ_W4_PRIO == 1 && G::WAVES == 8 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
-    __builtin_amdgcn_s_setprio(1);
   if constexpr (G::NG == 1) {  // one transform row: its partial outputs, both halves
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1473,10 +1215,10 @@ __device__ __forceinline__ void conv_body(
   W4_STAMP(3);
   // output rows 2ty (Y[0]) are final after group 2: stored while group 3 computes, with
   // their residual staged through LDS during group 2 (and the odd rows' during group 3)
-  // the resident trunk stages its residual in X's odd rows instead (AZ_W4_RXS)
-  constexpr bool SX = RSD && RES && AZ_W4_RXS;
-  constexpr bool STAGED = (RES && G::RES_FITS && !G::SPLIT && !RSD) || SX;
-  constexpr bool KEEPY = HOUT || XOUT;
+  // the resident trunk stages its residual in X's odd rows instead (SX; res_dma_x)
+  constexpr bool SX = RSD && RES;
+  constexpr bool STAGED = (RES && G::RES_FITS && !G::SPLIT) || SX;
+  constexpr bool KEEPY = XOUT;  // the epilogues leave the final values in Y for the X write-out
   run_group<G, 2, STAGED && !SX ? 0 : -1, RSD, SX ? 0 : -1>(S);
   W4_STAMP(4);
   W4T_STAMP(layer, 2);
@@ -1509,41 +1251,13 @@ __device__ __forceinline__ void conv_body(
         }
       }
   }
-  if constexpr (HOUT) {
-    // the next layer's input: its first two slices (channels 0-31 = column block 0's
-    // registers) into the input slots -- free since the last chunk's windows were read,
-    // before this layer's last two barriers -- and each wave's per-board max |y|
-    if (cb == 0) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int T = (e & 3) + 8 * (e >> 2) + 4 * h;
-          const int bd = T >> 4, ty = (T >> 2) & 3, tx = T & 3;
-          if (bd >= nb) continue;
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            *reinterpret_cast<float*>(S.lds + G::IN_OFF + (r >> 4) * G::IN_SLOT + bd * G::IN_BOARD +
-                                      (2 * ty + i + 1) * G::IN_ROW +
-                                      col_slot(2 * tx + j + 1) * 64 + (r & 15) * 4) =
-                S.Y[i][j][0][e];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      float m = E.bmax[i];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-      if (lane == 0) reinterpret_cast<float*>(S.lds + G::RNG_OFF)[wave * 4 + i] = m;
-    }
-  }
   if constexpr (HEADS) {
     // in_absmax is consumed (every thread read its entries in the prologue)
     if (threadIdx.x < G::BOARDS && (int)threadIdx.x < nb) in_absmax[b0 + threadIdx.x] = 0.0f;
     heads_epilogue<G>(S, ho, rt0, h, E.co);
     return;
   }
-  if (out_absmax && !HOUT) {  // the next layer's in_absmax: one atomic per (wave, board)
+  if (out_absmax) {  // the next layer's in_absmax: one atomic per (wave, board)
 #pragma unroll
     for (int i = 0; i < 2 * G::NRT; ++i) {
       float m = E.bmax[i];
@@ -1578,9 +1292,6 @@ __global__ __launch_bounds__(G::THREADS, 2 / G::NRT) void k_conv3x3_wino4(
 // drained (vmcnt(0)) and an L1 invalidate (buffer_inv sc0: the ping-pong buffers were read
 // by earlier layers) order it; per-board ranges ping-pong amax[0] / amax[1] as between the
 // per-layer launches.  Same arithmetic per layer: bit-identical to those launches.
-#ifndef AZ_W4_STAGGER
-#define AZ_W4_STAGGER 0
-#endif
 struct TrunkW4 {
   const char* const* wq;     // [n_convs] prepared weights (layer order)
   const float* const* bias;  // [n_convs]
@@ -1662,61 +1373,16 @@ __device__ __forceinline__ void stem_board(const float* __restrict__ planes,
   if (tid == 0) absmax[b] = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
 }
 
-// AlphaZeroNet's heads on this workgroup's NB boards of the tower's output y (just written
-// by this workgroup, after a layer_fence): heads_four with each board's activations read on
-// demand from y (L2), its partial sums in the workgroup's LDS -- the same code and order as
-// the separate heads kernel, so bit-identical priors / values.
-template <class G>
-__device__ __forceinline__ void trunk_heads(const float* __restrict__ y, int n_boards,
-                                            const HeadsOut& ho) {
-  constexpr int C = G::C, NB = G::BOARDS;
-  static_assert(NB <= azh::kQuarters && G::THREADS >= 64 * azh::kQuarters, "heads layout");
-  extern __shared__ float4 lds4[];
-  char* base = reinterpret_cast<char*>(lds4);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b0 = blockIdx.x * NB;
-  const int nb = n_boards - b0 < NB ? n_boards - b0 : NB;
-  const bool active = wave < azh::kQuarters, live = wave < NB && wave < nb;
-  const float4* hp = reinterpret_cast<const float4*>(
-      y + ((size_t)(b0 + (live ? wave : 0)) * 64 + lane) * C);
-  // p [NB][128] at 0, v [NB][64] at 1 KiB, lp [4][NB][65] at 2 KiB, hv [4][NB][64] at 4,352
-  static_assert(NB * 128 * 4 <= 1024 && 1024 + NB * 64 * 4 <= 2048 &&
-                    2048 + azh::kQuarters * NB * 65 * 4 <= 4352,
-                "heads scratch layout");
-  const azh::ScratchT<NB> L{reinterpret_cast<float(*)[128]>(base),
-                            reinterpret_cast<float(*)[64]>(base + 1024),
-                            reinterpret_cast<float(*)[NB][65]>(base + 2048),
-                            reinterpret_cast<float4(*)[NB][64]>(base + 4352)};
-  azh::heads_four<C, NB>([&](int c) { return hp[c]; }, lane, wave & (azh::kQuarters - 1),
-                         b0 + wave, live, active, ho.w, L, ho.priors, ho.values);
-}
-
-// HEADS: after the last conv (n_convs - 1, a block's second: odd; its output stored as in
-// any layer) each workgroup runs AlphaZeroNet's heads on its boards (trunk_heads: priors /
-// values bit-identical to az_conv3x3_wino4_heads_gpu and to the separate heads kernel) --
-// the tower and the heads in one launch, no kernel boundary before the last layer.  (The
-// heads in the last conv's epilogue, inlined here as a third body, spilled ~100 VGPRs into
-// the layer loop.)
-// AZ_W4_TRUNK_HEADS_EPI (HEADS launches): 1 = the last conv runs after the layer loop as the
-// heads-fused body (heads from the accumulators, as az_conv3x3_wino4_heads_gpu; no store and
-// read-back of the tower's output; 242 VGPRs, no spills): B = 1,024 evaluation 423.3 vs 424.6
-// us for the tower launch + heads-fused conv launch and 431.4 for the read-back form, bench
-// +0.2 %, bit-identical (profiles/r04_trunk_heads_epi_ab.json); 0 = the last conv in the loop,
-// then trunk_heads (the read-back form)
-#ifndef AZ_W4_TRUNK_HEADS_EPI
-#define AZ_W4_TRUNK_HEADS_EPI 1
-#endif
+// HEADS: the launch's last conv (n_convs - 1, a block's second: odd) runs after the layer loop
+// as the heads-fused body -- AlphaZeroNet's heads from the accumulators, as
+// az_conv3x3_wino4_heads_gpu (priors / values bit-identical to it and to the separate heads
+// kernel); the tower's output is neither stored nor read back -- the tower and the heads in one
+// launch, no kernel boundary before the last layer: 242 VGPRs, no spills
+// (profiles/r04_trunk_heads_epi_ab.json).  (The heads inlined into the layer loop's conv2 body
+// spilled ~100 VGPRs into the loop.)
 template <class G, bool HEADS = false>
 __global__ __launch_bounds__(G::THREADS, 2 / G::NRT) void k_trunk_wino4(TrunkW4 a,
                                                                       HeadsOut ho) {
-  constexpr bool EPI = HEADS && AZ_W4_TRUNK_HEADS_EPI;
-#if AZ_W4_STAGGER
-  // experiment: the second half of the grid (the second workgroup on each CU when every
-  // workgroup is resident) starts later, so the two co-resident workgroups' phases differ
-  if (blockIdx.x >= (gridDim.x + 1) / 2) {
-    for (int i = 0; i < AZ_W4_STAGGER; ++i) __builtin_amdgcn_s_sleep(8);  // 512 clocks each
-  }
-#endif
   if (a.planes) {  // the stem of this workgroup's boards first (its output never leaves L2)
     static_assert(G::THREADS >= 256 && G::C == 128, "stem_board's mapping");
     extern __shared__ float4 lds4[];
@@ -1726,107 +1392,57 @@ __global__ __launch_bounds__(G::THREADS, 2 / G::NRT) void k_trunk_wino4(TrunkW4 
       stem_board(a.planes, a.stem_w, a.stem_b, a.h_in, a.amax[0], b0 + bd, sp, sp + 64);
     layer_fence();
   }
+  // conv_body<G, RES, RELU, HEADS, RSD, XFILL, XOUT>: every layer is a ReLU conv on the resident
+  // input; conv1 (even i) reads X and writes t only into X; conv2 reads t from X, stages the
+  // residual h from global memory, writes h to global memory (the next block's residual) and
+  // into X.  A launch's first conv loads X (XFILL); its last writes none (no XOUT)
+  constexpr bool RES = true, RELU = true, FUSED = true, RSD = true, XFILL = true, XOUT = true;
   const float* h = a.h_in;
   int ob = 0;
-  const int n_loop = EPI ? a.n_convs - 1 : a.n_convs;
-  if constexpr (AZ_W4_RESIDENT) {
-    // the resident input: conv1 (even i) reads X, writes t only into X; conv2 reads t from X
-    // and the residual h from global memory, writes h to global memory (the next block's
-    // residual) and into X.  A launch's first conv loads X; its last writes none
-    for (int i = 0; i < n_loop; ++i) {
-      if (i > 0) layer_fence();
-      const bool xout = i + 1 < a.n_convs;
-      if ((i & 1) == 0) {
-        if (i == 0 && xout)
-          conv_body<G, false, true, false, true, false, false, true, true, true>(
-              h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
-              a.amax[0], a.amax[1], HeadsOut{}, i);
-        else if (i == 0)
-          conv_body<G, false, true, false, true, false, false, true, true, false>(
-              h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
-              a.amax[0], a.amax[1], HeadsOut{}, i);
-        else if (xout)
-          conv_body<G, false, true, false, true, false, false, true, false, true>(
-              h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
-              a.amax[0], a.amax[1], HeadsOut{}, i);
-        else
-          conv_body<G, false, true, false, true, false, false, true, false, false>(
-              h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
-              a.amax[0], a.amax[1], HeadsOut{}, i);
-      } else {
-        const bool last_heads = HEADS && i == a.n_convs - 1;
-        if (xout)
-          conv_body<G, true, true, false, true, false, false, true, false, true>(
-              a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, a.hb[ob], a.n_boards,
-              a.amax[1], last_heads ? nullptr : a.amax[0], HeadsOut{}, i);
-        else
-          conv_body<G, true, true, false, true, false, false, true, false, false>(
-              a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, a.hb[ob], a.n_boards,
-              a.amax[1], last_heads ? nullptr : a.amax[0], HeadsOut{}, i);
-        h = a.hb[ob];
-        ob ^= 1;
-      }
-    }
-    if constexpr (EPI) {
-      layer_fence();  // the last block's conv1 output in X, ordered for this workgroup
-      const int i = a.n_convs - 1;
-      conv_body<G, true, true, true, true, false, false, true, false, false>(
-          a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, nullptr, a.n_boards, a.amax[1],
-          nullptr, ho, i);
-    } else if constexpr (HEADS) {
-      layer_fence();
-      trunk_heads<G>(h, a.n_boards, ho);
-    }
-    return;
-  }
-  constexpr bool HO = AZ_W4_HANDOFF != 0 && G::BOARDS == 2 && G::SCALED;  // two-board fp16x2 only
+  const int n_loop = HEADS ? a.n_convs - 1 : a.n_convs;
   for (int i = 0; i < n_loop; ++i) {
     if (i > 0) layer_fence();
-    // a conv whose output the next conv reads hands it off through LDS (every conv but the
-    // launch's last); the first conv reads the stem's output from memory
-    const bool hout = HO && (i + 1 < a.n_convs);
+    const bool xout = i + 1 < a.n_convs;
     if ((i & 1) == 0) {
-      if (i == 0 && hout)
-        conv_body<G, false, true, false, true, false, HO>(
-            h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards, a.amax[0],
-            a.amax[1], HeadsOut{}, i);
+      if (i == 0 && xout)
+        conv_body<G, !RES, RELU, !FUSED, RSD, XFILL, XOUT>(
+            h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
+            a.amax[0], a.amax[1], HeadsOut{}, i);
       else if (i == 0)
-        conv_body<G, false, true, false, true>(h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]),
-                                               nullptr, a.t, a.n_boards,
-                                               a.amax[0], a.amax[1], HeadsOut{}, i);
-      else if (hout)
-        conv_body<G, false, true, false, true, HO, HO>(
-            h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards, a.amax[0],
-            a.amax[1], HeadsOut{}, i);
+        conv_body<G, !RES, RELU, !FUSED, RSD, XFILL, !XOUT>(
+            h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
+            a.amax[0], a.amax[1], HeadsOut{}, i);
+      else if (xout)
+        conv_body<G, !RES, RELU, !FUSED, RSD, !XFILL, XOUT>(
+            h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
+            a.amax[0], a.amax[1], HeadsOut{}, i);
       else
-        conv_body<G, false, true, false, true, HO, false>(
-            h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards, a.amax[0],
-            a.amax[1], HeadsOut{}, i);
+        conv_body<G, !RES, RELU, !FUSED, RSD, !XFILL, !XOUT>(
+            h, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), nullptr, a.t, a.n_boards,
+            a.amax[0], a.amax[1], HeadsOut{}, i);
     } else {
-      // the last layer of a HEADS launch keeps no range (nothing reads its output as a
-      // conv input): amax[0] stays as the stem / caller left it
+      // (never true: a HEADS launch's last conv runs after the loop.  The compiler does not
+      // fold the test away, and dropping it changes the HEADS kernels' code by an instruction)
       const bool last_heads = HEADS && i == a.n_convs - 1;
-      if (hout)
-        conv_body<G, true, true, false, true, HO, HO>(
-            a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, a.hb[ob], a.n_boards, a.amax[1],
-            last_heads ? nullptr : a.amax[0], HeadsOut{}, i);
+      if (xout)
+        conv_body<G, RES, RELU, !FUSED, RSD, !XFILL, XOUT>(
+            a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, a.hb[ob], a.n_boards,
+            a.amax[1], last_heads ? nullptr : a.amax[0], HeadsOut{}, i);
       else
-        conv_body<G, true, true, false, true, HO, false>(
-            a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, a.hb[ob], a.n_boards, a.amax[1],
-            last_heads ? nullptr : a.amax[0], HeadsOut{}, i);
+        conv_body<G, RES, RELU, !FUSED, RSD, !XFILL, !XOUT>(
+            a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, a.hb[ob], a.n_boards,
+            a.amax[1], last_heads ? nullptr : a.amax[0], HeadsOut{}, i);
       h = a.hb[ob];
       ob ^= 1;
     }
   }
-  if constexpr (EPI) {
-    layer_fence();  // the last block's first conv output (t) visible to this workgroup
+  if constexpr (HEADS) {
+    // the last layer keeps no range (nothing reads its output as a conv input)
+    layer_fence();  // the last block's conv1 output in X, ordered for this workgroup
     const int i = a.n_convs - 1;
-    conv_body<G, true, true, true, true, HO, false>(a.t, uniform_ptr(a.wq[i]),
-                                                    uniform_ptr(a.bias[i]), h, nullptr,
-                                                    a.n_boards, a.amax[1], nullptr, ho, i);
-  } else if constexpr (HEADS) {
-    layer_fence();  // the last layer's stores drained and visible to this workgroup's reads
-    trunk_heads<G>(h, a.n_boards, ho);
+    conv_body<G, RES, RELU, FUSED, RSD, !XFILL, !XOUT>(
+        a.t, uniform_ptr(a.wq[i]), uniform_ptr(a.bias[i]), h, nullptr, a.n_boards, a.amax[1],
+        nullptr, ho, i);
   }
 }
 

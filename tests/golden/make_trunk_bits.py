@@ -1,6 +1,6 @@
 """Generate tests/golden/trunk_bits.npz: the fp16x2 trunk's outputs on the seeded cases of
 tests/trunk_cases.py, recorded on an MI355X with the library of the commit BEFORE the
-single-issue fp32 forms of csrc/conv_wino4.hip (AZ_W4_F32S), so
+single-issue fp32 forms of csrc/conv_wino4.hip (the input transform's col_comb / combine_kx), so
 tests/test_trunk_f32_issue_gpu.py pins every later build to those bits.
 
     AZ_LIB_PATH=<that commit's libaz_othello.so> python tests/golden/make_trunk_bits.py [out.npz]
@@ -12,7 +12,8 @@ build id.
 The persistent trunk's contract is the per-layer launches' bits (tests/test_nn_gpu.py).  That
 commit's persistent trunk broke it at B = 5: board 4, alone in the last workgroup with an
 input range >= 64, got NaN into its top-left windows (an off-board window word x coefficient
-overflowed before the edge mask's x 0; fixed with AZ_W4_CMASK).  Where the recorded trunk
+overflowed before the edge mask's x 0; fixed by combine_kx's column masks in the
+coefficients).  Where the recorded trunk
 outputs differ from the recorded per-layer ones, the per-layer ones are stored for the trunk
 case too and the case is named in `trunk_cases_from_layers`."""
 import os

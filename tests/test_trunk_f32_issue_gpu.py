@@ -1,6 +1,7 @@
-"""The fp16x2 trunk after the single-issue fp32 forms of csrc/conv_wino4.hip (AZ_W4_F32S: the
-input transform's, the fold's and the epilogues' two-wide fp32 operations issued one element
-per instruction): the same IEEE operations, so the same results.
+"""The fp16x2 trunk after the single-issue fp32 forms of csrc/conv_wino4.hip (two-wide fp32
+operations issued one element per instruction: the input transform's ship -- col_comb,
+combine_kx -- the fold's and the epilogues' were measured too): the same IEEE operations, so
+the same results.
 
 On the seeded cases of tests/trunk_cases.py -- B = 1, 2, 3 and 5 boards (a half-empty two-board
 workgroup, a full one, odd tails), one residual block and all five, a random board, an all-zero

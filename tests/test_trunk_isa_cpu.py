@@ -1,5 +1,5 @@
-"""Build-time guard for the persistent trunk's fp32 issue forms (AZ_W4_F32S in
-csrc/conv_wino4.hip): both fp16x2 instantiations of k_trunk_wino4 in the built library hold the
+"""Build-time guard for the persistent trunk's fp32 issue forms (the single-issue
+col_comb / combine_kx of csrc/conv_wino4.hip): both fp16x2 instantiations of k_trunk_wino4 in the built library hold the
 packed-fp32 count the shipped default claims -- the input transform single-issue (no packed
 fp32 left in it), the fold, the epilogues and the heads packed as before -- use no scratch,
 and keep two waves per SIMD (at most 256 vector registers of the SIMD's 512 per lane).  CPU
@@ -21,8 +21,8 @@ OBJDUMP = os.path.join(scan.LLVM, "llvm-objdump")
 READELF = os.path.join(scan.LLVM, "llvm-readelf")
 # k_trunk_wino4<W4<AZ_CONV_FP16X2 = 2, 1, 2, 8, 4>, heads = false / true>
 FP16X2 = re.compile(r"k_trunk_wino4INS_2W4ILi2ELi1ELi2ELi8ELi4EEELb[01]E")
-# v_pk_{add,mul,fma}_f32 per kernel (without / with the fused heads) with the default
-# AZ_W4_F32S = 1; the commit before it: 2,976 / 1,992, every part single-issue: 0 / 0
+# v_pk_{add,mul,fma}_f32 per kernel (without / with the fused heads) with the single-issue
+# input transform; the commit before it: 2,976 / 1,992, every part single-issue: 0 / 0
 PACKED_F32_SHIPPED = {"Lb0E": 1514, "Lb1E": 1017}
 
 needs_tools = pytest.mark.skipif(
