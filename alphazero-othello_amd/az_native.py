@@ -153,6 +153,8 @@ SIGNATURES = {
     "oth_solve_deep_cpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _P, _P, _P],
     "oth_solve_deep_gpu": [_P, _P, _I64, _I32, _I32, _I32, _U64, _I32, _P, _P, _P, _P, _P, _P],
     "oth_solve_moves_cpu": [_P, _P, _I64, _I32, _I32, _U64, _P, _P, _P],
+    "oth_line_step_cpu": [_P, _P, _P, _P, _I64, _I32, _I32] + [_P] * 9,
+    "oth_line_step_gpu": [_P, _P, _P, _P, _I64, _I32, _I32] + [_P] * 9 + [_P],
     "az_leaf_solve_cpu": [_P, _P, _I64, _I32, _U64, _P],
     "az_leaf_solve_gpu": [_P, _P, _I64, _I32, _U64, _P, _P, _P],
     "az_leaf_solve_stats_gpu": [_P, _P, _P],

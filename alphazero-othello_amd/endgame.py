@@ -387,6 +387,114 @@ def exact_policy(values):
     return (hit / np.maximum(count, 1)).astype(np.float32)
 
 
+LINE_FIELDS = ("own", "opp", "pi", "act", "z")
+
+
+def _line_cpu(own, opp, max_empties, node_limit):
+    """optimal_line on the host: per ply one "optimal" table of every root
+    (_solve_moves_cpu; a finished root is skipped without a node) and one oth_line_step_cpu."""
+    n, stride = own.size, max(1, 2 * int(max_empties))
+    wo, wp = own.copy(), opp.copy()
+    count, done = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    score = np.full(n, nat.AZ_SOLVE_SKIPPED, np.int8)
+    rows = {"own": np.zeros(n * stride, np.uint64), "opp": np.zeros(n * stride, np.uint64),
+            "pi": np.zeros((n * stride, 65), np.float32), "act": np.zeros(n * stride, np.uint8),
+            "z": np.zeros(n * stride, np.float32)}
+    live = np.zeros(1, np.int32)
+    for ply in range(stride + 1):
+        values, sc, _ = _solve_moves_cpu(wo, wp, max_empties, nat.AZ_MOVES_OPTIMAL, node_limit)
+        nat.check(nat.lib.oth_line_step_cpu(
+            nat.ptr(wo), nat.ptr(wp), nat.ptr(values), nat.ptr(sc), n, stride, int(ply == 0),
+            nat.ptr(count), nat.ptr(done), nat.ptr(score),
+            *[nat.ptr(rows[k]) for k in LINE_FIELDS], nat.ptr(live)), "oth_line_step_cpu")
+        if live[0] == 0:
+            break
+    else:
+        raise RuntimeError("optimal_line: roots alive after 2 * max_empties plies")
+    keep = (np.arange(stride, dtype=np.int32)[None, :] < count[:, None]).reshape(-1)
+    out = {k: rows[k][keep] for k in LINE_FIELDS}
+    out["off"] = np.concatenate([[0], np.cumsum(count, dtype=np.int64)]).astype(np.int64)
+    out["score"] = score
+    return out
+
+
+def _line_gpu(own, opp, max_empties, node_limit):
+    """optimal_line on the device: per ply solve_moves_gpu_tensors over every root and one
+    oth_line_step_gpu (one lane per root).  The step adds one host read per ply, the number of
+    roots still alive, to those solve_moves_gpu_tensors makes itself (the sizes of its
+    expansion, one solver call per distinct root score); the final compaction of the rows
+    synchronises once more, after the loop."""
+    dev, n, stride = own.device, own.numel(), max(1, 2 * int(max_empties))
+    with torch.cuda.device(dev):
+        wo, wp = own.clone(), opp.clone()
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        count, done = z(n, torch.int32), z(n, torch.uint8)
+        score = torch.full((n,), nat.AZ_SOLVE_SKIPPED, dtype=torch.int8, device=dev)
+        rows = {"own": z(n * stride, torch.int64), "opp": z(n * stride, torch.int64),
+                "pi": z((n * stride, 65), torch.float32), "act": z(n * stride, torch.uint8),
+                "z": z(n * stride, torch.float32)}
+        live = z(1, torch.int32)
+        for ply in range(stride + 1):
+            values, sc, _ = solve_moves_gpu_tensors(wo, wp, max_empties, nat.AZ_MOVES_OPTIMAL,
+                                                    node_limit)
+            nat.check(nat.lib.oth_line_step_gpu(
+                nat.ptr(wo), nat.ptr(wp), nat.ptr(values.contiguous()), nat.ptr(sc.contiguous()),
+                n, stride, int(ply == 0), nat.ptr(count), nat.ptr(done), nat.ptr(score),
+                *[nat.ptr(rows[k]) for k in LINE_FIELDS], nat.ptr(live), nat.stream_ptr()),
+                "oth_line_step_gpu")
+            if int(live.item()) == 0:
+                break
+        else:
+            raise RuntimeError("optimal_line: roots alive after 2 * max_empties plies")
+        keep = (torch.arange(stride, dtype=torch.int32, device=dev)[None, :]
+                < count[:, None]).reshape(-1)
+        out = {k: rows[k][keep] for k in LINE_FIELDS}
+        out["off"] = torch.cat([z(1, torch.int64), torch.cumsum(count.to(torch.int64), 0)])
+        out["score"] = score
+    return out
+
+
+def optimal_line(own, opp, max_empties=12, device=None, node_limit=1 << 31):
+    """Every root (own = side to move, 0..max_empties <= 14 empties) played to the end of the
+    game along score-optimal moves: one row per ply, all roots' rows flattened in root order.
+    Returns a dict of
+      own, opp   the ply's position from its side to move,
+      pi         float32 [rows, 65] = exact_policy of the ply's solve_moves(mode="optimal")
+                 table: uniform over the score-optimal actions, one-hot on 64 where the side to
+                 move must pass and the opponent can place,
+      act        uint8, the move played = the lowest optimal action (the solvers' `best`),
+      z          float32 = sign(the exact score from the ply's side to move),
+      off        int64 [n + 1]: root i's rows are off[i] .. off[i + 1] - 1,
+      score      int8 [n], the root's exact disc difference.
+    A terminal root has no rows (score = its final difference).  A root with more empties or
+    overlapping boards has none and score AZ_SOLVE_SKIPPED; one whose search (at any ply) passes
+    `node_limit` has none and score AZ_SOLVE_ABORTED, as in `solve_moves`.  max_empties outside
+    0..14 is a ValueError.
+
+    Arrays, tensors and the device choice follow `solve`.  On the device every ply is the
+    existing solve_moves kernels over the roots and one oth_line_step_gpu; the host path runs
+    the same step (oth_line_step_cpu) over the host's tables, so both give the same arrays bit
+    for bit."""
+    if not 0 <= int(max_empties) <= nat.AZ_SOLVE_MAX_EMPTIES:
+        raise ValueError(f"max_empties={max_empties}: 0..{nat.AZ_SOLVE_MAX_EMPTIES}")
+    want_torch = isinstance(own, torch.Tensor)
+    dev = _pick_device(device, own, opp)
+    if dev.type == "cuda":
+        out = _line_gpu(_as_i64_tensor(own, dev), _as_i64_tensor(opp, dev), int(max_empties),
+                        node_limit)
+        if want_torch:
+            return out
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        out["own"], out["opp"] = out["own"].view(np.uint64), out["opp"].view(np.uint64)
+        return out
+    out = _line_cpu(_as_u64_numpy(own), _as_u64_numpy(opp), int(max_empties), node_limit)
+    if want_torch:
+        out["own"], out["opp"] = out["own"].view(np.int64), out["opp"].view(np.int64)
+        return {k: torch.from_numpy(np.ascontiguousarray(v)).to(own.device)
+                for k, v in out.items()}
+    return out
+
+
 def _check_solved(score, what):
     if (score == nat.AZ_SOLVE_ABORTED).any():
         raise RuntimeError(f"{what}: {int((score == nat.AZ_SOLVE_ABORTED).sum())} searches "

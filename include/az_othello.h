@@ -212,6 +212,34 @@ int oth_solve_moves_cpu(const uint64_t* own, const uint64_t* opp, int64_t n, int
                         int32_t mode, uint64_t node_limit, int8_t* values_o /* n*65 */,
                         int8_t* score_o, uint64_t* nodes_o);
 
+/* ---------------- the optimal line of a solved root, one ply per call ------------------
+ * endgame.optimal_line plays every root to the end of the game along score-optimal moves: per
+ * ply one OPTIMAL-mode table of all roots (above), then one call of this step (csrc/line_step.h;
+ * the device kernel takes one lane per root, the host entry point runs the same body, so the
+ * two agree bit for bit).  For every root i with done[i] == 0:
+ *   - score[i] a skipped / aborted code: root_score[i] gets it (an abort at a later ply also
+ *     sets count[i] = 0: no partial line), the root is done;
+ *   - no available action in values[i] (the game is over): the root is done;
+ *   - else row count[i] of the root (slot i * stride + count[i] of the row arrays) gets own,
+ *     opp, pi = 1 / k on the k available actions whose value is the row's maximum and 0
+ *     elsewhere (endgame.exact_policy), act = the lowest of them and z = sign(score[i]); the
+ *     action (64 = pass) is played into own[i] / opp[i], count[i] advances, and the root is done
+ *     when neither side can place.
+ * first != 0 (the roots' first ply) also writes root_score[i] = score[i].  A root that is
+ * done gets own = opp = ~0 (overlapping boards: every solver skips it without a node), so the
+ * next ply's table call costs nothing for it.  *live_o = the roots not done after the call (the
+ * device entry point zeroes and counts it on `stream`).  stride in 1..40 rows per root; a line
+ * of a root with E empties has at most 2 * E rows. */
+int oth_line_step_cpu(uint64_t* own, uint64_t* opp, const int8_t* values /* n*65 */,
+                      const int8_t* score, int64_t n, int32_t stride, int32_t first,
+                      int32_t* count, uint8_t* done, int8_t* root_score, uint64_t* row_own,
+                      uint64_t* row_opp, float* row_pi /* n*stride*65 */, uint8_t* row_act,
+                      float* row_z, int32_t* live_o);
+int oth_line_step_gpu(uint64_t* own, uint64_t* opp, const int8_t* values, const int8_t* score,
+                      int64_t n, int32_t stride, int32_t first, int32_t* count, uint8_t* done,
+                      int8_t* root_score, uint64_t* row_own, uint64_t* row_opp, float* row_pi,
+                      uint8_t* row_act, float* row_z, int32_t* live_o, void* stream);
+
 /* ---------------- exact values for late leaves of the search --------------------------
  * A pass between a leaf evaluation and the expansion that reads it (csrc/leaf_solve.hip).
  * Row r of nn_in is 64 floats in {-1, 0, +1}, the canonical planes of a leaf: own (the side
