@@ -24,7 +24,7 @@ SOURCES = ["csrc/board.hip", "csrc/engine.hip", "csrc/nn_fused.hip", "csrc/conv.
            "csrc/solve_moves.hip", "csrc/canon.hip", "csrc/line_step.hip"]
 HEADERS = ["csrc/bitboard.h", "csrc/common.h", "csrc/philox.h", "csrc/heads_az.h",
            "csrc/solve.h", "csrc/search.h", "csrc/records.h", "csrc/solve_deep.h",
-           "csrc/lane_search.h", "csrc/split_front.h", "csrc/line_step.h",
+           "csrc/lane_search.h", "csrc/split_front.h", "csrc/line_step.h", "csrc/negamax.h",
            "../include/az_othello.h"]
 OUT = os.path.join(HERE, "libaz_othello.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",

@@ -9,16 +9,19 @@
 // Every loop is bounded: a search ends after node_limit nodes at the latest, the lane loop
 // ends when the task counter passes the task count, and no lane waits for another.
 //
-// The search itself (Search, init, step and the kRun / kDone states) comes from the header of
-// its namespace (solve.h, search.h, solve_deep.h); step is found through its Search argument.
+// The search itself (Search, init, step) comes from the header of its namespace (solve.h,
+// search.h, solve_deep.h) and its kRun / kDone states from negamax.h; step is found through
+// its Search argument.
 #pragma once
 #include <algorithm>
 
 #include "common.h"
+#include "negamax.h"
 
 namespace azl {
 
-constexpr int kRun = 0, kDone = 1;  // Search::state, the same two values in every namespace
+using azn::kDone;
+using azn::kRun;
 constexpr int kLdsBytes = 160 * 1024;
 
 // A lane's column of the block's frame stack: WORDS 8-byte fields per frame, then (PACKED) one

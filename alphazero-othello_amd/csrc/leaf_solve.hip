@@ -45,7 +45,6 @@ constexpr size_t kStatsOffset = 64;  // bytes
 static_assert(AZ_LEAF_SOLVE_MAX_EMPTIES == kLeafFrames + 1 &&
                   AZ_LEAF_SOLVE_MAX_EMPTIES <= azd::kMaxEmpties,
               "include/az_othello.h and csrc/leaf_solve.hip disagree");
-static_assert(azd::kRun == azl::kRun && azd::kDone == azl::kDone, "lane_search.h's states");
 
 using Stack = azl::LdsStack<kWave, 3, true>;  // k_solve_deep's
 

@@ -1,7 +1,8 @@
 // search.h — depth-limited alpha-beta with a heuristic leaf evaluation, shared by
 // oth_search_cpu / oth_eval_cpu and the k_search / k_eval kernels (one source of truth, like
-// solve.h, whose per-position state machine this follows): step() advances ONE node of one
-// search, nothing recurses, and every loop around step() is bounded by the node limit.
+// solve.h, and like it a per-position state machine out of negamax.h's pieces): step()
+// advances ONE node of one search, nothing recurses, and every loop around step() is bounded
+// by the node limit.
 //
 // Value V(pos, depth) from the side to move's view, the first rule that matches:
 //   1. neither side has a placement: T(d) = sign(d) * (10000 + 100 * |d|), 0 for d = 0, with
@@ -27,16 +28,18 @@
 // the value; interior nodes try corners first, then ascending.  value and best are
 // properties of the minimax tree, not of the order.
 #pragma once
-#include "bitboard.h"
+#include "negamax.h"
 
 namespace azq {
 
+using azn::kCorners;
+using azn::kDone;
+using azn::kRun;
 constexpr int kSkipped = -32768;  // AZ_SEARCH_SKIPPED
 constexpr int kAborted = -32767;  // AZ_SEARCH_ABORTED
 constexpr int kMaxDepth = 10;     // AZ_SEARCH_MAX_DEPTH
 constexpr int kMaxFrames = kMaxDepth - 1;
 constexpr int kInf = 32000;  // outside every value (|value| <= 10000 + 100 * 64)
-constexpr uint64_t kCorners = 0x8100000000000081ull;
 
 // rows 0..3 of W; rows 4..7 mirror them
 constexpr int kW[4][8] = {{100, -20, 10, 5, 5, 10, -20, 100},
@@ -76,21 +79,8 @@ AZ_HD int evaluate(uint64_t own, uint64_t opp) {
   return heuristic(own, opp, lo, lp);
 }
 
-enum : int { kRun = 0, kDone = 1 };
-
-struct Search {
-  uint64_t own, opp;  // top frame: side to move, its opponent
-  uint64_t moves;     // top frame: placements not tried yet
-  uint64_t flips;     // capture set of the move that led to the top frame
-  uint64_t nodes;     // nodes visited so far
-  int alpha, beta, best;  // top frame's window (alpha already raised to best) and value so far
-  int sq, sign;       // square of the move that led here; 1 = reached through a pass as well
-  int depth;          // plies left below the top frame's position (>= 1)
-  int sp;             // frames on the stack below the top frame
-  int ret, ret_sq, pending;  // a child's value (parent's view) waiting to be taken
-  int state;          // kRun / kDone
-  int root_pass;      // the root itself had to pass: the top-level frame is the opponent's
-  int value, root_best;  // results once state == kDone
+struct Search : azn::WaitingFrame {
+  int depth;  // plies left below the top frame's position (>= 1)
 };
 
 AZ_HD uint64_t pack_frame(const Search& s) {
@@ -123,153 +113,53 @@ struct HostStack {
   }
 };
 
-AZ_HD void finish(Search& s, int value, int best) {
-  s.state = kDone;
-  s.value = value;
-  s.root_best = best;
-}
-
 // Start the search of one position to `depth` >= 1 plies.  Overlapping boards are not
 // searched; terminal roots finish here.
 AZ_HD void init(Search& s, uint64_t own, uint64_t opp, int depth) {
-  s.own = own;
-  s.opp = opp;
-  s.moves = 0;
-  s.flips = 0;
-  s.nodes = 0;
-  s.alpha = -kInf;
-  s.beta = kInf;
-  s.best = -kInf;
-  s.sq = 0;
-  s.sign = 0;
   s.depth = depth;
-  s.sp = 0;
-  s.ret = 0;
-  s.ret_sq = 0;
-  s.pending = 0;
-  s.root_pass = 0;
-  s.state = kRun;
-  s.value = 0;
-  s.root_best = azb::kPass;
-  if ((own & opp) != 0) {
-    finish(s, kSkipped, 255);
-    return;
-  }
-  s.nodes = 1;
-  uint64_t m = azb::legal(own, opp);
-  if (!m) {
-    m = azb::legal(opp, own);
-    if (!m) {
-      finish(s, terminal_value(azb::popc(own) - azb::popc(opp)), azb::kPass);
-      return;
-    }
-    s.own = opp;  // the root passes: search the opponent's position, negate at the end
-    s.opp = own;
-    s.root_pass = 1;
-    s.nodes = 2;
-  }
-  s.moves = m;
+  azn::start(s, own, opp, kInf, (own & opp) != 0, kSkipped,
+             terminal_value(azb::popc(own) - azb::popc(opp)));
 }
 
 // Advance one node.  max_frames = the stack's capacity (a full stack aborts the search
 // instead of writing past it; unreachable for depth <= max_frames + 1).
 template <class Stack>
 AZ_HD void step(Search& s, Stack& st, uint64_t node_limit, int max_frames) {
-  if (s.pending) {  // the value of the move tried last
-    s.pending = 0;
-    if (s.ret > s.best) {
-      s.best = s.ret;
-      if (s.sp == 0) s.root_best = s.ret_sq;
-      if (s.best > s.alpha) s.alpha = s.best;
-      if (s.best >= s.beta) s.moves = 0;
-    }
-  }
-  if (s.moves == 0) {  // this frame is finished: hand its value to the parent
-    if (s.sp == 0) {
-      finish(s, s.root_pass ? -s.best : s.best, s.root_pass ? azb::kPass : s.root_best);
-      return;
-    }
-    // undo the move: child boards are (opp ^ f, (own | bit) ^ f), swapped after a pass
-    const uint64_t bit = 1ull << s.sq;
-    const uint64_t mover = s.sign ? s.own : s.opp;
-    const uint64_t other = s.sign ? s.opp : s.own;
-    s.ret = s.sign ? s.best : -s.best;
-    s.ret_sq = s.sq;
-    s.pending = 1;
-    s.own = (mover ^ s.flips) & ~bit;
-    s.opp = other ^ s.flips;
-    --s.sp;
+  azn::take_handed(s);  // the value of the move tried last
+  if (s.moves == 0) {   // this frame is finished: hand its value to the parent
+    if (s.sp == 0) return azn::finish_root(s);
+    azn::hand(s, azn::undo(s), s.sq);
     uint64_t pk;
     st.get(s.sp, s.flips, s.moves, pk);
     unpack_frame(s, pk);
     return;
   }
-  // the next move of this frame
-  uint64_t m = s.moves;
-  if (s.sp > 0 && (m & kCorners)) m &= kCorners;
-  const int sq = __builtin_ctzll(m);
-  const uint64_t bit = 1ull << sq;
-  s.moves &= ~bit;
-  if (++s.nodes > node_limit) {
-    finish(s, kAborted, 255);
-    return;
-  }
-  const uint64_t f = azb::flips(s.own, s.opp, sq);
-  uint64_t cown = s.opp ^ f, copp = (s.own | bit) ^ f;
-  const int cdepth = s.depth - 1;
-  uint64_t cm = azb::legal(cown, copp);
+  // the next move of this frame: the root in ascending order, so its best is the lowest
+  const int sq = azn::pick(s.moves, s.sp > 0);
+  if (!azn::count_move(s, sq, node_limit, kAborted)) return;
+  azn::Child c = azn::make_child(s, sq, false);
   // the mover's own placements decide a pass / the end of the game, and are half of h
-  const uint64_t cm2 = (cdepth == 0 || !cm) ? azb::legal(copp, cown) : 0ull;
-  if (!(cm | cm2)) {  // the game ended with this move
-    s.ret = terminal_value(azb::popc(copp) - azb::popc(cown));
-    s.ret_sq = sq;
-    s.pending = 1;
-    return;
+  const uint64_t m2 = (s.depth == 1 || !c.moves) ? azn::mover_moves(c, false) : 0ull;
+  if (!(c.moves | m2))  // the game ended with this move
+    return azn::hand(s, terminal_value(azn::final_diff(c)), sq);
+  if (s.depth == 1)  // the horizon
+    return azn::hand(s, -heuristic(c.own, c.opp, c.moves, m2), sq);
+  if (!c.moves) {  // the opponent passes, the same plies left
+    c.moves = m2;
+    azn::pass(s, c);
   }
-  if (cdepth == 0) {  // the horizon
-    s.ret = -heuristic(cown, copp, cm, cm2);
-    s.ret_sq = sq;
-    s.pending = 1;
-    return;
-  }
-  int sign = 0;
-  if (!cm) {  // the opponent passes: the mover's side again, the same plies left
-    const uint64_t t = cown;
-    cown = copp;
-    copp = t;
-    cm = cm2;
-    sign = 1;
-    ++s.nodes;
-  }
-  if (s.sp >= max_frames) {
-    finish(s, kAborted, 255);
-    return;
-  }
+  if (!azn::room(s, max_frames, kAborted)) return;
   st.put(s.sp, s.flips, s.moves, pack_frame(s));
-  ++s.sp;
-  const int a = s.alpha, b = s.beta;
-  s.alpha = sign ? a : -b;
-  s.beta = sign ? b : -a;
-  s.best = -kInf;
-  s.own = cown;
-  s.opp = copp;
-  s.moves = cm;
-  s.flips = f;
-  s.sq = sq;
-  s.sign = sign;
-  s.depth = cdepth;
+  azn::enter(s, c, kInf);
+  --s.depth;
 }
 
 // One whole search on the host.
 inline void search_one(uint64_t own, uint64_t opp, int depth, uint64_t node_limit,
                        int16_t* value, uint8_t* best, uint64_t* nodes) {
   Search s;
-  HostStack st;
   init(s, own, opp, depth);
-  while (s.state == kRun) step(s, st, node_limit, kMaxFrames);
-  *value = (int16_t)s.value;
-  *best = (uint8_t)s.root_best;
-  if (nodes) *nodes = s.nodes;
+  azn::run_host<HostStack>(s, node_limit, kMaxFrames, value, best, nodes);
 }
 
 }  // namespace azq

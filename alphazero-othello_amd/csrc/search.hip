@@ -15,7 +15,6 @@
 static_assert(AZ_SEARCH_SKIPPED == azq::kSkipped && AZ_SEARCH_ABORTED == azq::kAborted &&
                   AZ_SEARCH_MAX_DEPTH == azq::kMaxDepth,
               "include/az_othello.h and csrc/search.h disagree");
-static_assert(azq::kRun == azl::kRun && azq::kDone == azl::kDone, "lane_search.h's states");
 
 namespace {
 
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(kSearchBlock) void k_search(
         azq::init(s, own[node], opp[node], depth_of ? (int)depth_of[node] : depth);
       },
       [&](const azq::Search& s) {
-        value_o[node] = (int16_t)s.value;
+        value_o[node] = (int16_t)s.score;
         best_o[node] = (uint8_t)s.root_best;
         if (nodes_o) nodes_o[node] = s.nodes;
       });

@@ -14,7 +14,6 @@
 static_assert(AZ_SOLVE_SKIPPED == azs::kSkipped && AZ_SOLVE_ABORTED == azs::kAborted &&
                   AZ_SOLVE_MAX_EMPTIES == azs::kMaxEmpties,
               "include/az_othello.h and csrc/solve.h disagree");
-static_assert(azs::kRun == azl::kRun && azs::kDone == azl::kDone, "lane_search.h's states");
 
 namespace {
 

@@ -1,9 +1,11 @@
 // solve_deep.h — windowed, move-ordered endgame search shared by oth_solve_deep_cpu and the
 // k_solve_deep kernel.  The same shape as solve.h (an iterative fail-soft negamax written as
 // a per-position state machine, the top frame in registers, the frames below it in a stack
-// the caller provides, no recursion, every loop around step() bounded by the node limit);
-// new are a root window and an ordering of the moves.  solve.h's search is untouched: its
-// lowest-square `best` and its node counts are pinned by tests.
+// the caller provides, no recursion, every loop around step() bounded by the node limit) out
+// of the same pieces (negamax.h: the pass, end-of-game and node rules, the window, the frame
+// word); its own are a root window and an ordering of the moves.  solve.h keeps its order and
+// its lowest-square `best`; every root's result and node count of both are pinned by
+// tests/golden/search_goldens.npz.
 //
 // Window.  The root is searched in (alpha, beta), -65 <= alpha < beta <= 65.  With s the true
 // score the result v is: v = s if alpha < s < beta; beta <= v <= s if s >= beta;
@@ -39,50 +41,26 @@
 // action (not necessarily the lowest); if v >= beta its value is >= beta; if v <= alpha it
 // is merely legal.  64 when the side to move has no placement.
 #pragma once
-#include "bitboard.h"
+#include "negamax.h"
 
 namespace azd {
 
+using azn::kDone;
+using azn::kRun;
 constexpr int kSkipped = -128;   // AZ_SOLVE_SKIPPED
 constexpr int kAborted = -127;   // AZ_SOLVE_ABORTED
 constexpr int kMaxEmpties = 20;  // AZ_SOLVE_DEEP_MAX_EMPTIES
 constexpr int kMaxFrames = kMaxEmpties - 1;
-constexpr int kInf = 65;  // outside every value (|value| <= 64)
+constexpr int kInf = azn::kInf;  // outside every value (|value| <= 64)
 constexpr int kOrderMin = 5;
 constexpr int kOrderSlots = 10;
-constexpr uint64_t kCorners = 0x8100000000000081ull;
 constexpr uint64_t kNoKeys = 0x0FFFFFFFFFFFFFFFull;  // ten empty slots: key 63 each
 
-enum : int { kRun = 0, kDone = 1 };
-
-struct Search {
-  uint64_t own, opp;  // top frame: side to move, its opponent
-  uint64_t moves;     // top frame: placements not tried yet
-  uint64_t order;     // top frame: ordered squares not tried yet (6 bits each, count in 60..63)
-  uint64_t flips;     // capture set of the move that led to the top frame
-  uint64_t probe;     // top frame: placements still to probe for the order (not stacked)
-  uint64_t keys;      // keys of the squares in `order` while probing (not stacked)
-  uint64_t nodes;     // nodes visited so far
-  int alpha, beta, best;  // top frame's window (alpha already raised to best) and value so far
-  int sq, sign;       // square of the move that led here; 1 = reached through a pass as well
-  int sp;             // frames on the stack below the top frame
-  int state;          // kRun / kDone
-  int root_pass;      // the root itself had to pass: the top-level frame is the opponent's
-  int score, root_best;  // results once state == kDone
+struct Search : azn::Frame {
+  uint64_t order;  // top frame: ordered squares not tried yet (6 bits each, count in 60..63)
+  uint64_t probe;  // top frame: placements still to probe for the order (not stacked)
+  uint64_t keys;   // keys of the squares in `order` while probing (not stacked)
 };
-
-AZ_HD uint32_t pack_frame(const Search& s) {
-  return (uint32_t)(s.alpha + kInf) | ((uint32_t)(s.beta + kInf) << 8) |
-         ((uint32_t)(s.best + kInf) << 16) | ((uint32_t)(s.sq | (s.sign << 6)) << 24);
-}
-
-AZ_HD void unpack_frame(Search& s, uint32_t w) {
-  s.alpha = (int)(w & 0xFF) - kInf;
-  s.beta = (int)((w >> 8) & 0xFF) - kInf;
-  s.best = (int)((w >> 16) & 0xFF) - kInf;
-  s.sq = (int)((w >> 24) & 63);
-  s.sign = (int)((w >> 30) & 1);
-}
 
 // the host's frame stack (the device's is in solve_deep.hip)
 struct HostStack {
@@ -102,15 +80,9 @@ struct HostStack {
   }
 };
 
-AZ_HD void finish(Search& s, int score, int best) {
-  s.state = kDone;
-  s.score = score;
-  s.root_best = best;
-}
-
-// A frame with placements m starts: decide whether its moves are probed first.
-AZ_HD void start_frame(Search& s, uint64_t m) {
-  s.moves = m;
+// The top frame starts with its placements s.moves: decide whether they are probed first.
+AZ_HD void start_frame(Search& s) {
+  const uint64_t m = s.moves;
   s.order = 0;
   s.keys = kNoKeys;
   const bool ordered = 64 - azb::popc(s.own | s.opp) >= kOrderMin && (m & (m - 1)) != 0;
@@ -135,54 +107,18 @@ AZ_HD void order_insert(Search& s, int sq, int k) {
 // searched (more than max_empties empties, overlapping boards) and terminal roots finish
 // here.
 AZ_HD void init(Search& s, uint64_t own, uint64_t opp, int max_empties, int alpha, int beta) {
-  s.own = own;
-  s.opp = opp;
-  s.moves = 0;
   s.order = 0;
-  s.flips = 0;
   s.probe = 0;
   s.keys = kNoKeys;
-  s.nodes = 0;
-  s.alpha = alpha;
-  s.beta = beta;
-  s.best = -kInf;
-  s.sq = 0;
-  s.sign = 0;
-  s.sp = 0;
-  s.root_pass = 0;
-  s.state = kRun;
-  s.score = 0;
-  s.root_best = azb::kPass;
-  if ((own & opp) != 0 || 64 - azb::popc(own | opp) > max_empties) {
-    finish(s, kSkipped, 255);
-    return;
-  }
-  s.nodes = 1;
-  uint64_t m = azb::legal(own, opp);
-  if (!m) {
-    m = azb::legal(opp, own);
-    if (!m) {
-      finish(s, azb::popc(own) - azb::popc(opp), azb::kPass);
-      return;
-    }
-    s.own = opp;  // the root passes: search the opponent's position, negate at the end
-    s.opp = own;
-    s.alpha = -beta;
-    s.beta = -alpha;
-    s.root_pass = 1;
-    s.nodes = 2;
-  }
-  start_frame(s, m);
+  s.moves = azn::start(s, own, opp, alpha, beta, kInf,
+                       (own & opp) != 0 || 64 - azb::popc(own | opp) > max_empties, kSkipped,
+                       azb::popc(own) - azb::popc(opp));
+  if (s.moves) start_frame(s);
 }
 
-// Take the value `ret` of the move `sq` just tried into the top frame.
-AZ_HD void take(Search& s, int ret, int sq) {
-  if (ret > s.best) {
-    s.best = ret;
-    if (s.sp == 0) s.root_best = sq;
-    if (s.best > s.alpha) s.alpha = s.best;
-    if (s.best >= s.beta) s.moves = 0;
-  }
+// The next ordered square leaves the order word.
+AZ_HD void order_pop(Search& s) {
+  s.order = ((s.order & ((1ull << 60) - 1)) >> 6) | (((s.order >> 60) - 1) << 60);
 }
 
 // Advance one step: a finished frame's value handed to its parent, then a probe or a move
@@ -190,95 +126,45 @@ AZ_HD void take(Search& s, int ret, int sq) {
 // writing past it; unreachable for max_empties <= max_frames + 1).
 template <class Stack>
 AZ_HD void step(Search& s, Stack& st, uint64_t node_limit, int max_frames) {
-  if (s.moves == 0) {  // this frame is finished: hand its value to the parent
-    if (s.sp == 0) {
-      finish(s, s.root_pass ? -s.best : s.best, s.root_pass ? azb::kPass : s.root_best);
-      return;
-    }
-    // undo the move: child boards are (opp ^ f, (own | bit) ^ f), swapped after a pass
-    const int sq = s.sq;
-    const uint64_t bit = 1ull << sq;
-    const uint64_t mover = s.sign ? s.own : s.opp;
-    const uint64_t other = s.sign ? s.opp : s.own;
-    const int ret = s.sign ? s.best : -s.best;
-    s.own = (mover ^ s.flips) & ~bit;
-    s.opp = other ^ s.flips;
-    --s.sp;
+  if (s.moves == 0) {  // this frame is finished: its parent takes its value in this step
+    if (s.sp == 0) return azn::finish_root(s);
+    const int sq = s.sq, ret = azn::undo(s);
     uint32_t pk;
     st.get(s.sp, s.flips, s.moves, s.order, pk);
-    unpack_frame(s, pk);
-    take(s, ret, sq);
+    azn::unpack_frame(s, pk);
+    azn::take(s, ret, sq);
     if (s.moves == 0) return;  // the parent is finished as well: the next step's work
   }
   // the square of this step: the next probe, else the next move of this frame
-  const bool probing = s.probe != 0;
-  int sq;
+  const bool probing = s.probe != 0, ordered = (s.order >> 60) != 0;
+  const int sq = probing ? __builtin_ctzll(s.probe)
+                         : (ordered ? (int)(s.order & 63) : azn::pick(s.moves, true));
+  azn::Child c = azn::make_child(s, sq, true);
   if (probing) {
-    sq = __builtin_ctzll(s.probe);
-  } else if (s.order >> 60) {
-    sq = (int)(s.order & 63);
-  } else {
-    uint64_t m = s.moves;
-    if (m & kCorners) m &= kCorners;
-    sq = __builtin_ctzll(m);
-  }
-  const uint64_t bit = 1ull << sq;
-  const uint64_t f = azb::flips(s.own, s.opp, sq);
-  uint64_t cown = s.opp ^ f, copp = (s.own | bit) ^ f;
-  const bool full = (cown | copp) == ~0ull;
-  uint64_t cm = full ? 0ull : azb::legal(cown, copp);
-  if (probing) {
+    const uint64_t bit = 1ull << sq;
     s.probe &= ~bit;
-    order_insert(s, sq, 2 * azb::popc(cm) + ((bit & kCorners) ? 0 : 1));
+    order_insert(s, sq, 2 * azb::popc(c.moves) + ((bit & azn::kCorners) ? 0 : 1));
     return;
   }
-  if (s.order >> 60) s.order = ((s.order & ((1ull << 60) - 1)) >> 6) | (((s.order >> 60) - 1) << 60);
-  s.moves &= ~bit;
-  if (++s.nodes > node_limit) {
-    finish(s, kAborted, 255);
-    return;
+  if (ordered) order_pop(s);
+  if (!azn::count_move(s, sq, node_limit, kAborted)) return;
+  if (!c.moves) {
+    c.moves = azn::mover_moves(c, true);
+    if (!c.moves) return azn::take(s, azn::final_diff(c), sq);  // the game ended with this move
+    azn::pass(s, c);
   }
-  int sign = 0;
-  if (!cm) {
-    cm = full ? 0ull : azb::legal(copp, cown);
-    if (!cm) {  // the game ended with this move
-      take(s, azb::popc(copp) - azb::popc(cown), sq);
-      return;
-    }
-    const uint64_t t = cown;  // the opponent passes: the mover's side again
-    cown = copp;
-    copp = t;
-    sign = 1;
-    ++s.nodes;
-  }
-  if (s.sp >= max_frames) {
-    finish(s, kAborted, 255);
-    return;
-  }
-  st.put(s.sp, s.flips, s.moves, s.order, pack_frame(s));
-  ++s.sp;
-  const int a = s.alpha, b = s.beta;
-  s.alpha = sign ? a : -b;
-  s.beta = sign ? b : -a;
-  s.best = -kInf;
-  s.own = cown;
-  s.opp = copp;
-  s.flips = f;
-  s.sq = sq;
-  s.sign = sign;
-  start_frame(s, cm);
+  if (!azn::room(s, max_frames, kAborted)) return;
+  st.put(s.sp, s.flips, s.moves, s.order, azn::pack_frame(s));
+  azn::enter(s, c, kInf);
+  start_frame(s);
 }
 
 // One whole search on the host.
 inline void solve_one(uint64_t own, uint64_t opp, int max_empties, int alpha, int beta,
                       uint64_t node_limit, int8_t* score, uint8_t* best, uint64_t* nodes) {
   Search s;
-  HostStack st;
   init(s, own, opp, max_empties, alpha, beta);
-  while (s.state == kRun) step(s, st, node_limit, kMaxFrames);
-  *score = (int8_t)s.score;
-  *best = (uint8_t)s.root_best;
-  if (nodes) *nodes = s.nodes;
+  azn::run_host<HostStack>(s, node_limit, kMaxFrames, score, best, nodes);
 }
 
 }  // namespace azd

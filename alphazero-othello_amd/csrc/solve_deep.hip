@@ -25,7 +25,6 @@
 static_assert(AZ_SOLVE_SKIPPED == azd::kSkipped && AZ_SOLVE_ABORTED == azd::kAborted &&
                   AZ_SOLVE_DEEP_MAX_EMPTIES == azd::kMaxEmpties,
               "include/az_othello.h and csrc/solve_deep.h disagree");
-static_assert(azd::kRun == azl::kRun && azd::kDone == azl::kDone, "lane_search.h's states");
 
 namespace {
 
