@@ -112,3 +112,132 @@ def MockNet(salt=0):
             values.copy_(v)
 
     return _MockNet()
+
+
+# ---- the sharp family ------------------------------------------------------------------
+# What a trained net puts out and the mock above never does: a few moves hold all the mass,
+# most priors are exactly 0 or far below the renormalisation threshold, equal priors are
+# common, and values saturate.  With x = canonical + 1:
+#
+#     h_a = (A @ x)_a mod 1021,   k = (B @ x) mod 2001
+#     prior_a = 2^-((h_a // 4) mod 24)   if h_a mod 4 == 1   (1 .. 2^-23: ties are common)
+#             = 2^-44                    if h_a mod 4 == 0   (a row of these sums to a
+#                                                             non-zero value below 1e-12)
+#             = 0.0                      otherwise
+#     value   = +1, -1, 0 for k mod 4 = 0, 1, 2, and (k - 1000) / 1024 for k mod 4 = 3
+#
+# Integer arithmetic and exact powers of two: numpy, the reference, the oracle and the device
+# agree bit for bit, as for the mock above.
+#
+# The residues 0 and 1 of h_a mod 4 were first drawn up the other way round (0 = the powers of
+# two, 1 = 2^-44).  With that assignment every one of the seven root positions of
+# tests/golden/make_sharp_goldens.py has a legal move of residue 0, so no Dirichlet-noised
+# root had net priors at or below the renormalisation threshold, which
+# tests/test_sharp_cpu.py requires of the fixtures (the float64 noise path over zero net
+# priors).  As it stands, the 55-ply root's three legal moves have residues (2, 2, 0): net
+# priors (0, 0, 2^-44).  Nothing else about the policy changed.
+_TINY = np.float32(2.0 ** -44)
+_POW2 = (2.0 ** -np.arange(24, dtype=np.float64)).astype(np.float32)
+
+
+def sharp_eval(canonical, salt=0):
+    """canonical: int array [..., 64] with values in {-1, 0, +1}.
+    Returns priors float32 [..., 65] and values float64 [...] (float32-exact)."""
+    A, B = _mats(salt)
+    x = np.asarray(canonical).astype(np.int64) + 1
+    h = (x @ A.T) % 1021
+    m = h % 4
+    priors = np.where(m == 1, _POW2[(h // 4) % 24],
+                      np.where(m == 0, _TINY, np.float32(0.0))).astype(np.float32)
+    k = (x @ B) % 2001
+    km = k % 4
+    values = np.where(km == 0, 1.0, np.where(km == 1, -1.0, np.where(
+        km == 2, 0.0, (k - 1000) / 1024.0)))
+    return priors, values
+
+
+class SharpPolicy:
+    """Duck-typed `policy` for the reference MCTS (policy.inference(state, player))."""
+
+    def inference(self, state, current_player):
+        canon = (current_player * np.asarray(state)).reshape(-1)
+        p, v = sharp_eval(canon)
+        return p.astype(np.float32), float(v)
+
+
+class SharpPolicyNet(SharpPolicy):
+    """Constructible the way one_self_play builds its net (self_play_worker.py:43-46)."""
+
+    def __init__(self, **cfg):
+        pass
+
+    def load_state_dict(self, sd):
+        return None
+
+    def eval(self):
+        return self
+
+    def get_config(self):
+        return {}
+
+
+def sharp_eval_planes(nn_in):
+    """Evaluator for the engine: nn_in float [B, 64] canonical planes (+1/-1/0)."""
+    x = np.rint(np.asarray(nn_in, np.float32)).astype(np.int64).reshape(-1, 64)
+    p, v = sharp_eval(x)
+    return p, v.astype(np.float32)
+
+
+def _sharp_torch(planes, At, Bt, pow2):
+    """sharp_eval on device: exact float64 integer matmuls, the powers of two looked up."""
+    import torch
+
+    x = torch.round(planes.double()) + 1.0
+    h = torch.remainder(x @ At, 1021.0).long()
+    k = torch.remainder(x @ Bt, 2001.0).long()
+    m = h % 4
+    zero = torch.zeros((), dtype=torch.float32, device=planes.device)
+    pr = torch.where(m == 1, pow2[(h // 4) % 24], torch.where(m == 0, pow2[24], zero))
+    km = k % 4
+    lin = ((k - 1000).double() / 1024.0).float()
+    one = torch.ones((), dtype=torch.float32, device=planes.device)
+    va = torch.where(km == 0, one, torch.where(km == 1, -one, torch.where(km == 2, zero, lin)))
+    return pr.contiguous(), va.contiguous()
+
+
+def _sharp_consts(salt, device=None):
+    import torch
+
+    A, B = _mats(salt)
+    return (torch.as_tensor(A.T, dtype=torch.float64, device=device),
+            torch.as_tensor(B, dtype=torch.float64, device=device),
+            torch.as_tensor(np.append(_POW2, _TINY), dtype=torch.float32, device=device))
+
+
+def sharp_eval_torch(planes, salt=0):
+    """planes: float32 [G, 64] -> (priors f32 [G, 65], values f32 [G]), as mock_eval_torch."""
+    return _sharp_torch(planes, *_sharp_consts(salt, planes.device))
+
+
+def SharpNet(salt=0):
+    """The sharp policy as a module BatchedSelfPlay evaluates (fold=False, evaluate_planes),
+    its constants resident on the device so the step is graph-capturable."""
+    import torch
+
+    class _SharpNet(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            At, Bt, pow2 = _sharp_consts(salt)
+            self.register_buffer("At", At)
+            self.register_buffer("Bt", Bt)
+            self.register_buffer("pow2", pow2)
+
+        def evaluate_planes(self, planes):
+            return _sharp_torch(planes, self.At, self.Bt, self.pow2)
+
+        def evaluate_into(self, planes, priors, values):
+            p, v = self.evaluate_planes(planes)
+            priors.copy_(p)
+            values.copy_(v)
+
+    return _SharpNet()

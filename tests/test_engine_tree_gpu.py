@@ -19,11 +19,13 @@ they reach terminal nodes, pass nodes, overflowing arenas and re-chosen overflow
 Left out: the second source of the overflow counter, a descent deeper than kMaxPath = 64
 nodes; no Othello search of these sizes gets 64 plies below its root.
 """
+import functools
+
 import numpy as np
 import pytest
 
 import tree_cases as tc
-from mock_policy import MockNet, mock_eval_torch
+from mock_policy import MockNet, mock_eval_torch, sharp_eval_torch
 
 pytestmark = pytest.mark.gpu
 
@@ -31,19 +33,19 @@ nat = pytest.importorskip("az_native")
 from engine import BatchedSelfPlay, Engine  # noqa: E402
 
 
-def step_plain(e):
+def step_plain(e, evaluate=mock_eval_torch):
     e.select()
-    pr, va = mock_eval_torch(e.nn_in)
+    pr, va = evaluate(e.nn_in)
     e.priors.copy_(pr)
     e.values.copy_(va)
     e.expand()
     e.play()
 
 
-def step_fused(e):
+def step_fused(e, evaluate=mock_eval_torch):
     """The drop-in MCTS's fused iteration: the last select's leaves, then this one's descents."""
     e.select_expand()
-    pr, va = mock_eval_torch(e.nn_in)
+    pr, va = evaluate(e.nn_in)
     e.priors.copy_(pr)
     e.values.copy_(va)
 
@@ -155,8 +157,8 @@ def overflow_engine(K, sims):
     return e
 
 
-def check_overflow_case(K, sims, step):
-    script = tc.overflow_script(K, sims)
+def check_overflow_case(K, sims, step, script=None):
+    script = script or tc.overflow_script(K, sims)
     e = overflow_engine(K, sims)
     biggest = replay(e, script, step)
     assert (biggest <= tc.CAPACITY).all() and biggest[1] > tc.CAPACITY - 33
@@ -175,6 +177,37 @@ def test_arena_overflow_follows_the_capacity_rule(K, sims):
 @pytest.mark.parametrize("sims", [s for K, s in tc.OVERFLOW_PARAMS if K == 1])
 def test_arena_overflow_fused_select_expand(sims):
     check_overflow_case(1, sims, step_fused)
+
+
+# ---- the sharp policy ---------------------------------------------------------------
+# mock_policy.sharp_eval: priors of exactly 0, of 2^-44 and equal powers of two, values of
+# exactly +-1 and 0 (tests/test_sharp_cpu.py counts what that reaches in a search).  Whole
+# trees, so a sibling group left unnormalised or a tie taken at another child shows at the
+# node where it happened and not only in the root's counts.
+
+step_plain_sharp = functools.partial(step_plain, evaluate=sharp_eval_torch)
+step_fused_sharp = functools.partial(step_fused, evaluate=sharp_eval_torch)
+
+
+@pytest.mark.parametrize("K,c_puct,eps", tc.ROOMY_PARAMS)
+def test_whole_trees_match_oracle_sharp(K, c_puct, eps):
+    e = roomy_engine(K, c_puct, eps)
+    replay(e, tc.roomy_script_sharp(K, c_puct, eps), step_plain_sharp)
+    c = e.counters()
+    assert c["arena_overflows"] == 0 and c["simulations"] == 3 * sum(tc.ROOMY_SCHEDULE)
+
+
+@pytest.mark.parametrize("K,c_puct,eps", tc.ROOMY_PARAMS)
+def test_whole_trees_match_oracle_fused_select_expand_sharp(K, c_puct, eps):
+    e = roomy_engine(K, c_puct, eps)
+    replay(e, tc.roomy_script_sharp(K, c_puct, eps), step_fused_sharp)
+    c = e.counters()
+    assert c["arena_overflows"] == 0 and c["simulations"] == 3 * sum(tc.ROOMY_SCHEDULE)
+
+
+@pytest.mark.parametrize("K,sims", tc.OVERFLOW_PARAMS_SHARP)
+def test_arena_overflow_follows_the_capacity_rule_sharp(K, sims):
+    check_overflow_case(K, sims, step_plain_sharp, tc.overflow_script_sharp(K, sims))
 
 
 # ---- the guards -------------------------------------------------------------------

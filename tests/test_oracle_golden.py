@@ -87,21 +87,23 @@ def test_d4_tables_consistent():
         assert (t.reshape(-1) == d["sym_board"][s]).all()
 
 
-def replay_case(d, c):
-    """Re-run one reference MCTS golden case on the oracle with the recorded draws."""
+def replay_case(d, c, policy=None, mcts=SeqMCTS):
+    """Re-run one reference MCTS golden case on the oracle with the recorded draws (policy:
+    the one the fixture was recorded with, the mock by default; mcts: SeqMCTS or a subclass
+    of it).  Returns the oracle."""
     rows = np.nonzero(d["log_case"] == c)[0]
     lo, hi = d["log_offsets"][c], d["log_offsets"][c + 1]
     nlo, nhi = d["noise_offsets"][c], d["noise_offsets"][c + 1]
     rng = LogRng(d["log_kind"][lo:hi], d["log_a"][lo:hi], d["log_b"][lo:hi],
                  d["noise"][nlo:nhi])
     r0 = rows[0]
-    mp = MockPolicy()
+    mp = policy or MockPolicy()
 
     def evaluate(own, opp, player):
         return mp.inference(ob.to_state(own, opp, player), player)
 
-    m = SeqMCTS(float(d["c_puct"][r0]), int(d["sims"][r0]), evaluate, dirichlet_alpha=1.0,
-                dirichlet_epsilon=float(d["eps"][r0]), rng=rng)
+    m = mcts(float(d["c_puct"][r0]), int(d["sims"][r0]), evaluate, dirichlet_alpha=1.0,
+             dirichlet_epsilon=float(d["eps"][r0]), rng=rng)
     for r in rows:
         own, opp = own_opp(d["pos"][r], d["neg"][r], d["player"][r])
         probs = m.search(int(own), int(opp), int(d["player"][r]), float(d["temp"][r]))
@@ -113,6 +115,7 @@ def replay_case(d, c):
         if r != rows[-1]:
             m.make_move(a)
     assert rng.i == len(rng.kinds)
+    return m
 
 
 @pytest.mark.parametrize("case", range(28))
@@ -122,22 +125,23 @@ def test_mcts_cases_match_reference(case):
     replay_case(d, case)
 
 
-def replay_vl_case(d, c):
+def replay_vl_case(d, c, policy=None, mcts=SeqMCTS):
     """One multi-leaf (virtual-loss) golden case: the reference's threaded search forced
-    into the engine's interleaving (tests/golden/make_vl_goldens.py), on the oracle."""
+    into the engine's interleaving (tests/golden/make_vl_goldens.py), on the oracle (policy
+    and mcts as in replay_case).  Returns the oracle."""
     rows = np.nonzero(d["log_case"] == c)[0]
     nlo, nhi = d["noise_offsets"][c], d["noise_offsets"][c + 1]
     n = nhi - nlo
     rng = LogRng(np.zeros(n, np.int32), np.arange(n, dtype=np.float64), np.zeros(n, np.int64),
                  d["noise"][nlo:nhi])
     r0 = rows[0]
-    mp = MockPolicy()
+    mp = policy or MockPolicy()
 
     def evaluate(own, opp, player):
         return mp.inference(ob.to_state(own, opp, player), player)
 
-    m = SeqMCTS(float(d["c_puct"][r0]), int(d["sims"][r0]), evaluate, dirichlet_alpha=1.0,
-                dirichlet_epsilon=float(d["eps"][r0]), rng=rng, leaves_per_step=int(d["k"][r0]))
+    m = mcts(float(d["c_puct"][r0]), int(d["sims"][r0]), evaluate, dirichlet_alpha=1.0,
+             dirichlet_epsilon=float(d["eps"][r0]), rng=rng, leaves_per_step=int(d["k"][r0]))
     for r in rows:
         own, opp = own_opp(d["pos"][r], d["neg"][r], d["player"][r])
         probs = m.search(int(own), int(opp), int(d["player"][r]), 1.0)
@@ -148,6 +152,7 @@ def replay_vl_case(d, c):
         if r != rows[-1]:
             m.make_move(int(np.argmax(d["counts"][r])))
     assert rng.i == len(rng.kinds)
+    return m
 
 
 @pytest.mark.parametrize("case", range(28))

@@ -16,7 +16,7 @@ from collections import namedtuple
 import numpy as np
 
 from conftest import load_golden
-from mock_policy import mock_eval
+from mock_policy import mock_eval, sharp_eval
 from oracle.mcts import SeqMCTS
 
 INIT_OWN, INIT_OPP = 0x0000000810000000, 0x0000001008000000
@@ -33,6 +33,8 @@ LATE_ROOT = (0, 54)
 # (leaves per step, simulations of the overflowing slot); its neighbours search 10
 OVERFLOW_PARAMS = [(K, S) for K in (1, 4) for S in (40, 120, 300)]
 NEIGHBOUR_SIMS = 10
+# the same under the sharp policy (mock_policy.sharp_eval: zero, tiny and equal priors, +-1 values)
+OVERFLOW_PARAMS_SHARP = [(1, 120), (4, 120)]
 
 Step = namedtuple("Step", "kind arg tree overflows")
 _FIELDS = ("own", "opp", "legal", "N", "W", "prior", "action", "term", "tval")
@@ -59,11 +61,20 @@ class Tree:
         return 0.0 if self.N[r] == 0 else self.W[r] / self.N[r]
 
 
+def _canon(own, opp):
+    return (((np.uint64(own) >> _BITS) & np.uint64(1)).astype(np.int64)
+            - ((np.uint64(opp) >> _BITS) & np.uint64(1)).astype(np.int64))
+
+
 def evaluate(own, opp, player):
     """The mock policy on the canonical board (own stones +1), as the engine's rows see it."""
-    canon = (((np.uint64(own) >> _BITS) & np.uint64(1)).astype(np.int64)
-             - ((np.uint64(opp) >> _BITS) & np.uint64(1)).astype(np.int64))
-    p, v = mock_eval(canon)
+    p, v = mock_eval(_canon(own, opp))
+    return p.astype(np.float32), float(v)
+
+
+def evaluate_sharp(own, opp, player):
+    """The sharp policy, the same way."""
+    p, v = sharp_eval(_canon(own, opp))
     return p.astype(np.float32), float(v)
 
 
@@ -129,7 +140,7 @@ def run_schedule(o, root, schedule):
 
 
 @functools.lru_cache(maxsize=None)
-def roomy_script(K, c_puct, eps):
+def roomy_script(K, c_puct, eps, evaluate=evaluate):
     """Per root of roomy_roots(): its Steps under ROOMY_SCHEDULE."""
     out = []
     for slot, root in enumerate(roomy_roots()):
@@ -139,8 +150,13 @@ def roomy_script(K, c_puct, eps):
     return out
 
 
+def roomy_script_sharp(K, c_puct, eps):
+    """roomy_script with the sharp policy: the same roots, noise and schedule."""
+    return roomy_script(K, c_puct, eps, evaluate_sharp)
+
+
 @functools.lru_cache(maxsize=None)
-def overflow_script(K, sims):
+def overflow_script(K, sims, evaluate=evaluate):
     """Three slots from the initial position: slot 1 searches `sims` twice (one re-root
     between) in a CAPACITY-node arena, slots 0 and 2 search NEIGHBOUR_SIMS in the reference's
     unbounded tree (which CAPACITY nodes hold with room to spare)."""
@@ -150,6 +166,11 @@ def overflow_script(K, sims):
     full = run_schedule(SeqMCTS(2.0, 0, evaluate, leaves_per_step=K, node_capacity=CAPACITY),
                         root, (sims, sims))
     return [near, full, near]
+
+
+def overflow_script_sharp(K, sims):
+    """overflow_script with the sharp policy."""
+    return overflow_script(K, sims, evaluate_sharp)
 
 
 def export_of(tree):
